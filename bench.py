@@ -21,7 +21,14 @@ step of the multi-rank context is  partials -> ONE all-reduce of the packed payl
 owned by the library, csrc/comm.hip) -> finish.  BASELINE configs[3] is `--gpus 4 --n1 4096 --n2-local 1024`;
 configs[4] (masked grid) is `--masked --n1 2048 --n2-local 2048 --m 32` (divide --n2-local by the rank count).
 
-Prints ONE JSON line on rank 0 (see the task contract): metric/value/... plus
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line on rank 0: metric, value, unit, higher_is_better,
+dtype, ms_per_step (wall time of one timed step), the configuration and the last step's ELBO / eigensolver counters.
+`--dump-outputs DIR` also writes what the last timed step returned to its caller, as float64 .npy files: elbo.npy (1,),
+grad.npy (5,) = d ELBO / d (ell1, ell2, s1, s2, sigma2), theta.npy (5,) = the hyper-parameters that step was evaluated at, and
+raw_params.npy (5,) = the Adam fit loop's raw parameters after its update.  The inputs are seeded: the same arguments give the
+same inputs on every run.
+
+`--full` adds everything else to the line (each part takes runs of its own; --no-extras / --no-cpu drop parts of it):
   roofline          live HIP-event timing of the projection launch (the only pass over Y) vs the gfx950 fp64 MFMA roofline;
                     `traffic` = PMC bytes of the committed rocprofv3 passes, only while they match the kernel source at HEAD
   stages_us         per-launch-group breakdown of one step (HIP events on the launch stream, plain launches)
@@ -202,7 +209,7 @@ def source_sha():
 
 def pmc_traffic(n1, n2_loc, m):
     """HBM bytes per launch of the roofline kernel from the committed rocprofv3 PMC passes (separate FETCH_SIZE / WRITE_SIZE
-    runs of this same command, profiles/r2_pmc_traffic.json written by tools/pmc_traffic.py).  None -- and the reason -- when
+    runs of this same command with --full, profiles/r2_pmc_traffic.json written by tools/pmc_traffic.py).  None -- and the reason -- when
     the passes are absent, were taken on another kernel source than HEAD's, or on another launch shape."""
     path = os.path.join(ROOT, "profiles", "r3_pmc_traffic.json")
     if not os.path.exists(path):
@@ -221,7 +228,7 @@ def pmc_traffic(n1, n2_loc, m):
 
 def rocprof_kernel_us(kernel):
     """Average duration (us) of a kernel in the committed rocprofv3 --kernel-trace --stats summary of this same command
-    (profiles/r3_step_kernel_stats.csv), or None."""
+    with --full (profiles/r3_step_kernel_stats.csv; the projection launches by itself only in the per-stage loop), or None."""
     import csv
     path = os.path.join(ROOT, "profiles", "r3_step_kernel_stats.csv")
     try:
@@ -278,7 +285,14 @@ def self_launch(args, argv):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy in float64 (the step's outputs are float64 host values)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.atleast_1d(np.asarray(a, dtype=np.float64)))
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -291,17 +305,31 @@ def main():
     ap.add_argument("--kind", default="rbf")
     ap.add_argument("--masked", action="store_true", help="BASELINE configs[4]: Bernoulli(0.7) mask, B0 cells, masked step")
     ap.add_argument("--cold", action="store_true", help="disable the eigensolver warm start")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip cold_ms_per_step / m_d_sweep / kron_solve / factor_build")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline: per-stage timing and "
+                                                        "roofline, the extra workloads and the CPU baseline (see the module "
+                                                        "docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip cold_ms_per_step / m_d_sweep / kron_solve / "
+                                                             "factor_build and the other extra workloads")
     ap.add_argument("--strong", action="store_true", help="strong scaling on BASELINE configs[3]'s grid: a fixed n1 x n2 grid "
                                                           "(default 4096 x 4096; --n1 / --n2 change it) whose rows are split over the ranks")
     ap.add_argument("--n2", type=int, default=None, help="global number of grid rows of the --strong grid")
     ap.add_argument("--backend", default="auto", help="auto (RCCL communicator owned by the library when the node has >= N GPUs, "
                                                       "the measured path; otherwise the gloo rehearsal) | nccl | gloo (N > 1 ranks "
                                                       "sharing GPUs through the host-callback transport; never a reported number)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
+
+
+def main():
+    args = parse_args()
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         sys.exit(self_launch(args, sys.argv[1:]))            # (before torch is imported: this process never touches the GPU)
@@ -426,7 +454,7 @@ def main():
         else:
             elbo, g, info = eng.elbo_step(Y, yy, th)       # multi-rank context: partials -> all-reduce -> finish inside
         opt.update(g)                                     # softplus chain rule + Adam
-        return elbo, info
+        return elbo, g, info, th
 
     def barrier():
         if world > 1:
@@ -438,7 +466,7 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        elbo, info = one_step()
+        elbo, grad, info, theta = one_step()
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -446,10 +474,12 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"elbo": elbo, "grad": grad, "theta": theta, "raw_params": opt.x})
 
     # live per-launch-group timing (HIP events on the launch stream, plain launches), separate short loop
     stages_us = {}
-    if not args.masked:
+    if args.full and not args.masked:
         eng.profile(True)
         nprof = max(5, min(50, args.steps))
         for _ in range(nprof):
@@ -476,12 +506,13 @@ def main():
             "rehearsal": rehearsal,
             "elbo_last": elbo,
             "jacobi": {"sweeps": info["sweeps"], "rounds": info["rounds"], "jitter": info["jitter"], "polished": info.get("polished")},
-            "stages_us": stages_us,
-            "stages_note": ("HIP events around plain launches in the library's profiling mode, where every launch group is its own "
-                            "launch; in the timed region above the step is one graph replay in which the projection of Y and the "
-                            "[C;C1;C2] products run as extra workgroups (riders) of the row-QR / Ritz launches"),
         }
-        if not args.masked:
+        if args.full:
+            out["stages_us"] = stages_us
+            out["stages_note"] = ("HIP events around plain launches in the library's profiling mode, where every launch group is "
+                                  "its own launch; in the timed region above the step is one graph replay in which the projection "
+                                  "of Y and the [C;C1;C2] products run as extra workgroups (riders) of the row-QR / Ritz launches")
+        if args.full and not args.masked:
             flops = algorithmic_flops(n1, n2_loc, m, m)
             dom = max(stages_us, key=stages_us.get)
             proj_tflops = flops[PROJ] / (stages_us[PROJ] * 1e-6) / 1e12
@@ -505,7 +536,7 @@ def main():
                 "step_frac_of_fp64_peak": step_flops / (ms_per_step * 1e-3) / 1e12 / FP64_PEAK_TFLOPS,
                 "step_hbm_floor_bytes": 8 * n1 * n2_loc + 8 * 2 * 2 * (m * n1 + m * n2_loc) + 8 * 4 * m * m,
             }
-        if world == 1 and not args.no_extras and not args.masked:
+        if args.full and world == 1 and not args.no_extras and not args.masked:
             out["cold_ms_per_step"] = timed_loop(eng, Y, yy, args.kind, x1, x2, m, warm=False, steps=40, warmup=5)
             # (40 warm-up steps: the warm chains settle -- ranks, row counts, their captured graphs -- over the first few dozen steps)
             out["m_d_sweep"] = {str(md): timed_loop(eng, Y, yy, args.kind, x1, x2, md, warm=True, steps=100, warmup=40)
@@ -520,9 +551,9 @@ def main():
             out["masked_iter"] = masked_iter_bench(eng, D)
             out["kron_solve"] = kron_solve_bench(eng, 1024)
             out["factor_build"] = factor_build_bench(eng)
-        if not args.no_cpu and world == 1 and not args.masked:
+        if args.full and not args.no_cpu and world == 1 and not args.masked:
             out["cpu_baseline"] = cpu_baseline(n1, n2_loc, m, args.kind, THETA0)
-        elif not args.no_cpu:
+        elif args.full and not args.no_cpu:
             out["cpu_baseline"] = None
     if world > 1:
         dist.barrier()

@@ -37,3 +37,27 @@ def test_algorithmic_flops_of_the_headline_shape():
     f = bench.algorithmic_flops(1024, 1024, 128, 128)
     total = sum(v for v in f.values() if isinstance(v, (int, float)))
     assert 0.8e9 < total < 1.1e9          # DESIGN / VERDICT: 0.927 GFLOP per step at 1024 x 1024, m_d = 128
+
+
+def test_plain_run_is_the_default_and_steps_must_be_positive():
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit as e:
+            assert e.code == 2
+        else:
+            raise AssertionError(f"{bad} was accepted")
+
+
+def test_dump_outputs_writes_float64_npy(tmp_path):
+    d = tmp_path / "outs"
+    bench.dump_outputs(str(d), {"elbo": -891.5, "grad": np.arange(5.0), "theta": [0.2, 0.2, 1.0, 1.0, 0.0026]})
+    assert sorted(p.name for p in d.iterdir()) == ["elbo.npy", "grad.npy", "theta.npy"]
+    e = np.load(d / "elbo.npy")
+    assert e.dtype == np.float64 and e.shape == (1,) and e[0] == -891.5
+    assert np.array_equal(np.load(d / "grad.npy"), np.arange(5.0))
+    assert np.load(d / "theta.npy").dtype == np.float64

@@ -50,8 +50,12 @@ def test_dense_oracle_regenerates_golden(path):
     dm = D.DenseKron(g["X"], g["y"], str(g["basis"]), str(g["kind"]), torch.tensor(g["grid1"]).to(mesh_dt),
                      torch.tensor(g["grid2"]).to(mesh_dt), raw=g["raw"])
     e, gr = dm.elbo_and_grad()
-    assert abs(e.item() - g["elbo"]) <= 1e-12 * abs(g["elbo"])
-    assert rel(gr.numpy(), g["grad_raw"]) < 1e-10
+    # The B1 case is ill-conditioned: its dense ELBO / gradient move by up to 4.2e-11 / 1.5e-10 with the host BLAS's code path
+    # and thread count (MKL AVX-512 / AVX2 / SSE4.2 kernels, 1-16 threads), so a bound at the golden's own rounding only holds on
+    # the CPU that wrote it.  Its bounds sit ~10x above that spread; the B0 cases stay within 1e-14 on every path.
+    tol_elbo, tol_grad = (5e-10, 2e-9) if str(g["basis"]) == "b1" else (1e-12, 1e-10)
+    assert abs(e.item() - g["elbo"]) <= tol_elbo * abs(g["elbo"])
+    assert rel(gr.numpy(), g["grad_raw"]) < tol_grad
 
 
 @pytest.mark.parametrize("path", MASK_CASES, ids=lambda p: os.path.basename(p)[7:-4])

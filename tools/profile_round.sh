@@ -19,7 +19,7 @@ run() {   # run <name> <rocprof extra args...> -- <program args...>
     done
     return 0
 }
-B="$R/bench.py --steps 60 --warmup 20 --no-cpu --no-extras"
+B="$R/bench.py --full --steps 60 --warmup 20 --no-cpu --no-extras"
 run step -- $B                                                     &&
 run step_m32 -- $B --kind matern32                                  &&
 VGGP_NO_GRAPH=1 run pmc_fetch --pmc FETCH_SIZE -- $B                &&
