@@ -79,6 +79,25 @@ extern "C" {
 #define VGGP_FLAG_BLOCK_JACOBI 2
 #define VGGP_FLAG_SCATTERED 4      /* x1[k], x2[k] are the coordinates of N = n1 = n2 scattered POINTS (not grid axes): only        */
                                    /* vggp_elbo_step_scattered and the *_masked read-outs apply                                      */
+/* Paired (general) inducing points -- GriddedMatern12SVGP / Matern12SVGP with a Z that is no cartesian grid
+ * (gridded_kronecker_structure.py:235-264, :396-438; bound kronecker_structure.py:249-278).  grid1[i], grid2[i] are the two
+ * coordinates of inducing point i; m1 = m2 = M, 1 <= M <= 16384; both bases VGGP_BASIS_POINTS (the per-dimension m <= 256 cap does
+ * not apply); combines with VGGP_FLAG_SCATTERED.  kernel = kernel_1 * kernel_2 on active dims 0 / 1, so
+ *     Kuu = s (K1 o K2) (Hadamard),  Kuf[i, k] = s k1(z_i1, x_k1) k2(z_i2, x_k2),  s = s1 s2,
+ * factored densely in M-space; the jitter follows psd_safe_cholesky on Kuu itself (0, 1e-8, 1e-7, 1e-6 added to its diagonal;
+ * reported in vggp_info.jitter1).  The plan allocates O(M^2 + M n_d) (full grid) / O(M^2 + N) (scattered) doubles once.
+ * On a paired context:
+ *   vggp_elbo_step (full grid Y [n2][n1]) / vggp_elbo_step_scattered (y [N])   value + theta-gradient; one host synchronisation
+ *                                                            (a Kuu that needs jitter is refactored at the next level)
+ *   vggp_zgrad / vggp_zgrad_scattered     gz1 = dE/dZ[:, 0], gz2 = dE/dZ[:, 1], each [M] (same Y / y as the step)
+ *   vggp_set_inducing(dim, z, M)          moves one coordinate column of Z without re-planning
+ *   vggp_qv_masked                        q(u) mean and variance, [M] each
+ *   vggp_qv_cov_masked                    q(u) covariance Kuu Sigma^-1 Kuu, [M][M]
+ *   vggp_readout_masked                   C_d is [mv_d][M]; Kvu[(a, b), i] = s C1[a][i] C2[b][i] (face-split, flat a mv2 + b)
+ *   vggp_posterior_masked, vggp_posterior_cov_masked   posterior(x*) from k(x*, Z)
+ * Every other step or read-out (vggp_qv, vggp_qv_cov, vggp_readout, vggp_posterior, vggp_posterior_cov, the masked steps, the
+ * partials / finish pair) returns VGGP_EINVAL, and so does a paired step on an n_ranks > 1 context. */
+#define VGGP_FLAG_PAIRED_Z 8
 
 typedef struct vggp_ctx vggp_ctx;
 

@@ -134,6 +134,7 @@ extern "C" int vggp_destroy(vggp_ctx* c) {
     }
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     vg_masked_free(c);
+    vg_paired_free(c);
     vg_comm_destroy(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->arena) (void)hipFree(c->arena);
@@ -315,6 +316,23 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
     if (!c || !desc) { vg_set_error("vggp_plan: null argument"); return VGGP_EINVAL; }
     VG_ENTER_DEVICE(c->device);
     int rc;
+    if (desc->flags & VGGP_FLAG_PAIRED_Z) {        // paired inducing points: a workspace of their own (paired.hip), no per-dimension plan
+        c->planned = false;
+        graphs_clear(c);
+        VG_HIP(hipDeviceSynchronize());
+        c->have_partials = c->have_step = c->have_masked = false;
+        c->acc_valid = false; c->last_payload = nullptr;
+        c->is_paired = false;
+        if ((rc = vg_paired_plan(c, desc))) return rc;
+        c->desc = *desc;
+        c->desc.x1 = c->desc.x2 = c->desc.grid1 = c->desc.grid2 = nullptr;
+        c->desc.n_total = (desc->flags & VGGP_FLAG_SCATTERED) ? desc->n1 : desc->n1 * desc->n2;     // (single-rank: all observations)
+        c->payload_len = 0;
+        c->is_paired = true;
+        c->planned = true;
+        return VGGP_OK;
+    }
+    if (c->is_paired || c->paired) { VG_HIP(hipDeviceSynchronize()); vg_paired_free(c); c->is_paired = false; }
     if ((rc = check_dim(desc->kind1, desc->basis1, desc->n1, desc->m1, "dimension 1"))) return rc;
     if ((rc = check_dim(desc->kind2, desc->basis2, desc->n2, desc->m2, "dimension 2"))) return rc;
     VG_REQUIRE(desc->x1 && desc->x2, "vggp_plan: null coordinate arrays");
@@ -393,6 +411,11 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
 // the Gram matrices as little as a small move of the lengthscale does, and the subspace start checks itself (VG_ESUBMISS).  This
 // is what an optimiser that trains Z (kronecker_structure.py:303-304) calls between steps.
 extern "C" int vggp_set_inducing(vggp_ctx* c, int dim, const double* z, int64_t m) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_set_inducing(c, dim, z, m);
+    }
     if (!c || !c->planned) { vg_set_error("vggp_set_inducing: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(dim == 0 || dim == 1, "vggp_set_inducing: dim must be 0 or 1");
     VgDim& d = c->d[dim];
@@ -1616,6 +1639,7 @@ static int finish_collect(vggp_ctx* c, double* elbo_out, double grad_out[5], vgg
 }
 
 extern "C" int vggp_elbo_partials(vggp_ctx* c, const double* Y, const double theta[5], double* payload, void* stream) {
+    VG_NOT_PAIRED(c, "vggp_elbo_partials");
     if (!c || !c->planned) { vg_set_error("vggp_elbo_partials: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(Y && theta && payload, "vggp_elbo_partials: null argument");
     VG_ENTER_DEVICE(c->device);
@@ -1642,6 +1666,7 @@ static int elbo_finish_once(vggp_ctx* c, const double* payload, double yy_total,
                             double* elbo_out, double grad_out[5], vggp_info* info, void* stream);
 extern "C" int vggp_elbo_finish(vggp_ctx* c, const double* payload, double yy_total, const double theta[5],
                                 double* elbo_out, double grad_out[5], vggp_info* info, void* stream) {
+    VG_NOT_PAIRED(c, "vggp_elbo_finish");
     int rc = elbo_finish_once(c, payload, yy_total, theta, elbo_out, grad_out, info, stream);
     if (rc == VG_ESUBMISS) rc = elbo_finish_once(c, payload, yy_total, theta, elbo_out, grad_out, info, stream);   // cold, same payload
     if (rc == VG_ESUBMISS) { vg_set_error("the eigensolver chain failed twice on the same step"); rc = VGGP_ENOCONV; }
@@ -1708,6 +1733,11 @@ static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const d
 // since the last step; the Gram matrices depend on nothing else) skips the attempt.
 extern "C" int vggp_elbo_step(vggp_ctx* c, const double* Y, double yy_total, const double theta[5], double* elbo_out,
                               double grad_out[5], vggp_info* info, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_step(c, Y, yy_total, theta, elbo_out, grad_out, info, stream ? (hipStream_t)stream : c->own_stream, false);
+    }
     if (c && c->planned && theta) {
         bool jump = false;
         for (int k = 0; k < 2; ++k) jump = jump || (c->last_ell[k] > 0.0 && std::fabs(theta[k] / c->last_ell[k] - 1.0) > 0.05);
@@ -1944,6 +1974,7 @@ static int build_RQ(vggp_ctx* c, hipStream_t st) {
 }
 
 extern "C" int vggp_qv(vggp_ctx* c, double* mean, double* var, void* stream) {
+    VG_NOT_PAIRED(c, "vggp_qv");
     if (!c || !c->have_step) { vg_set_error("vggp_qv: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(mean && var, "vggp_qv: null output");
     VG_ENTER_DEVICE(c->device);
@@ -1983,6 +2014,7 @@ __global__ void vg_kron_rows_kernel(const double* R1, const double* R2, const do
 }
 
 extern "C" int vggp_qv_cov(vggp_ctx* c, double* cov, void* stream) {
+    VG_NOT_PAIRED(c, "vggp_qv_cov");
     if (!c || !c->have_step) { vg_set_error("vggp_qv_cov: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(cov, "vggp_qv_cov: null output");
     VG_ENTER_DEVICE(c->device);
@@ -2010,6 +2042,7 @@ extern "C" int vggp_qv_cov(vggp_ctx* c, double* cov, void* stream) {
 // posterior at scattered points, processed in chunks so the workspace stays bounded
 extern "C" int vggp_posterior(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var,
                               void* stream) {
+    VG_NOT_PAIRED(c, "vggp_posterior");
     if (!c || !c->have_step) { vg_set_error("vggp_posterior: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(xs1 && xs2 && mean && var && ns >= 0, "vggp_posterior: bad argument");
     VG_ENTER_DEVICE(c->device);
@@ -2118,6 +2151,7 @@ static int posterior_factors(vggp_ctx* c, const double* xs1, const double* xs2, 
 }
 
 extern "C" int vggp_posterior_cov(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* cov, void* stream) {
+    VG_NOT_PAIRED(c, "vggp_posterior_cov");
     if (!c || !c->have_step) { vg_set_error("vggp_posterior_cov: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(xs1 && xs2 && cov && ns >= 1, "vggp_posterior_cov: bad argument");
     const long m1 = c->desc.m1, m2 = c->desc.m2, M = m1 * m2;
@@ -2154,6 +2188,7 @@ extern "C" int vggp_posterior_cov(vggp_ctx* c, const double* xs1, const double* 
 // var = s1 s2 (kd1 kd2^T + (T1 o T1)^T W (T2 o T2)), W = D - 1 (literal) or 1/D - 1.
 extern "C" int vggp_readout(vggp_ctx* c, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1,
                             const double* kd2, double* mean, double* var, int flags, void* stream) {
+    VG_NOT_PAIRED(c, "vggp_readout");
     if (!c || !c->have_step) { vg_set_error("vggp_readout: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(C1 && C2 && kd1 && kd2 && mean && var && mv1 >= 1 && mv2 >= 1, "vggp_readout: bad argument");
     VG_ENTER_DEVICE(c->device);
@@ -2493,6 +2528,11 @@ int vg_trsm_batch(const VgTrsmSpec* sp, int n, hipStream_t st) { return trsm_bat
 // Uses the resident state of the last vggp_elbo_step on the same Y (warm-basis accuracy, like the lengthscale gradient); one
 // extra pass over Y (B1 Y^T), ~25 small launches.
 extern "C" int vggp_zgrad(vggp_ctx* c, const double* Y, double* gz1, double* gz2, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_zgrad(c, Y, gz1, gz2, stream ? (hipStream_t)stream : c->own_stream, false);
+    }
     if (!c || !c->have_step) { vg_set_error("vggp_zgrad: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(Y && gz1 && gz2, "vggp_zgrad: null argument");
     // Row-sharded job: every term of g is a sum over observations, so each rank forms the part of ITS rows -- the columns of dimension

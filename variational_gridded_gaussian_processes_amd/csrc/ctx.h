@@ -63,6 +63,8 @@ struct vggp_ctx {
     long payload_len = 0;
     bool have_partials = false, have_step = false, have_masked = false;
     void* masked = nullptr;          // VgMasked workspace (masked.hip), allocated on first use
+    void* paired = nullptr;          // VgPaired workspace (paired.hip): allocated by a plan with VGGP_FLAG_PAIRED_Z
+    bool is_paired = false;          // the current plan is a paired one: only the entries listed in vggp.h apply
     // pinned host staging
     double* h_theta = nullptr;
     HostOut* h_out = nullptr;
@@ -144,6 +146,27 @@ int vg_blocked_chol_inverse(const VgDenseChol& w, hipStream_t st);
 int vg_partials_enqueue(vggp_ctx* c, const double* Y, double* payload, hipStream_t st, bool reduce = true, bool extrap = false, bool fused = false,
                         bool apply_ns = false, int early = 0);      // early: 1 = thin chain, 2 = regular warm chains ([C;C1;C2] is then the first rider)
 void vg_masked_free(vggp_ctx* c);
+// paired inducing points (paired.hip; VGGP_FLAG_PAIRED_Z): the entries of vggp.h that apply to a paired plan forward here
+int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc);
+void vg_paired_free(vggp_ctx* c);
+int vg_paired_set_inducing(vggp_ctx* c, int dim, const double* z, int64_t m);
+int vg_paired_step(vggp_ctx* c, const double* Y, double yy, const double theta[5], double* elbo_out, double grad_out[5],
+                   vggp_info* info, hipStream_t st, bool scattered_entry);
+int vg_paired_zgrad(vggp_ctx* c, const double* Y, double* gz1, double* gz2, hipStream_t st, bool scattered_entry);
+int vg_paired_qv(vggp_ctx* c, double* mean, double* var, hipStream_t st);
+int vg_paired_qv_cov(vggp_ctx* c, double* cov, hipStream_t st);
+int vg_paired_readout(vggp_ctx* c, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1, const double* kd2,
+                      double* mean, double* var, int flags, hipStream_t st);
+int vg_paired_posterior(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var, hipStream_t st);
+int vg_paired_posterior_cov(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* cov, hipStream_t st);
+// entries that have no paired meaning: VGGP_EINVAL with a message
+#define VG_NOT_PAIRED(c, fn)                                                                                            \
+    do {                                                                                                                \
+        if ((c) && (c)->is_paired) {                                                                                    \
+            vg_set_error("%s: not available on a context planned with VGGP_FLAG_PAIRED_Z (see vggp.h)", fn);          \
+            return VGGP_EINVAL;                                                                                         \
+        }                                                                                                               \
+    } while (0)
 void vg_masked_new_plan(vggp_ctx* c);
 // batch of triangular solves, each in place on its X (api.hip trsm_batch: element (row k, column c) at X[k * sk + c * sc])
 #define VG_TRSM_BLK 128

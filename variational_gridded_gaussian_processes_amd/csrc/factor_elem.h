@@ -29,6 +29,36 @@ __device__ __forceinline__ void vg_kappa(int kind, double dist, double inv_ell, 
     }
 }
 
+// The same profile at the signed offset d = z - x, with its derivative in z as well: dz = d kappa / dz (0 at d = 0, as autograd
+// differentiates |d| there).  Used by the paired inducing points (paired.hip), whose gradient runs through the coordinates of Z.
+__device__ __forceinline__ void vg_kappa_z(int kind, double d, double inv_ell, double& v, double& dv, double& dz) {
+    const double r = fabs(d) * inv_ell;
+    const double sg = d > 0.0 ? inv_ell : (d < 0.0 ? -inv_ell : 0.0);
+    if (kind == VGGP_KIND_MATERN12) {
+        const double e = exp(-r);
+        v = e;
+        dv = e * r * inv_ell;
+        dz = -e * sg;
+    } else if (kind == VGGP_KIND_MATERN32) {
+        const double a = 1.7320508075688772 * r;
+        const double e = exp(-a);
+        v = (1.0 + a) * e;
+        dv = a * a * e * inv_ell;
+        dz = -a * e * 1.7320508075688772 * sg;
+    } else if (kind == VGGP_KIND_MATERN52) {
+        const double a = 2.23606797749979 * r;
+        const double e = exp(-a);
+        v = (1.0 + a + a * a * (1.0 / 3.0)) * e;
+        dv = (a * a * (1.0 / 3.0)) * (1.0 + a) * e * inv_ell;
+        dz = -(a * (1.0 / 3.0)) * (1.0 + a) * e * 2.23606797749979 * sg;
+    } else {   // RBF
+        const double e = exp(-0.5 * r * r);
+        v = e;
+        dv = e * r * r * inv_ell;
+        dz = -e * r * sg;
+    }
+}
+
 // B0 cell-integral cross-covariance, cell k = (a, b], point x (kronecker_structure.py:768-790)
 __device__ __forceinline__ void vg_b0_A(double a, double b, double x, double ell, double& v, double& dv) {
     const double ua = fabs(x - a), ub = fabs(x - b);

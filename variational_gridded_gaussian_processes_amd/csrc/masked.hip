@@ -438,6 +438,7 @@ static int dense_chol_inverse(vggp_ctx* c, VgMasked& w, hipStream_t st) {
 extern "C" int vggp_elbo_step_masked(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs,
                                      const double theta[5], double* elbo_out, double grad_out[5], vggp_info* info,
                                      void* stream) {
+    VG_NOT_PAIRED(c, "vggp_elbo_step_masked");
     if (!c || !c->planned) { vg_set_error("vggp_elbo_step_masked: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(Ym && W && theta && elbo_out && grad_out, "vggp_elbo_step_masked: null argument");
     c->have_masked = false;          // a failed step must not leave an earlier step's state readable (qv_masked / posterior_masked)
@@ -558,6 +559,11 @@ extern "C" int vggp_elbo_step_masked(vggp_ctx* c, const double* Ym, const double
 // points (desc.n_total = the number of points over all ranks, yy = the global sum of squares) -- two all-reduces, see below.
 extern "C" int vggp_elbo_step_scattered(vggp_ctx* c, const double* y, double yy, const double theta[5], double* elbo_out,
                                         double grad_out[5], vggp_info* info, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_step(c, y, yy, theta, elbo_out, grad_out, info, stream ? (hipStream_t)stream : c->own_stream, true);
+    }
     if (!c || !c->planned) { vg_set_error("vggp_elbo_step_scattered: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(y && theta && elbo_out && grad_out, "vggp_elbo_step_scattered: null argument");
     VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "vggp_elbo_step_scattered: plan the context with VGGP_FLAG_SCATTERED");
@@ -704,6 +710,11 @@ __global__ void vgm_scal_kernel(double* x, long n, double a) {
 // Abar = L0^-T G_B and Kbar = -1/2 L0^-T (G_B B^T) L0^-1; the contraction with d kappa / d z is vggp_zgrad's.  One extra
 // M x M x N product (U) on top of the step's three; workspace 2 M N doubles.
 extern "C" int vggp_zgrad_scattered(vggp_ctx* c, const double* y, double* gz1, double* gz2, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_zgrad(c, y, gz1, gz2, stream ? (hipStream_t)stream : c->own_stream, true);
+    }
     if (!c || !c->have_masked || !c->masked || !(c->desc.flags & VGGP_FLAG_SCATTERED)) {
         vg_set_error("vggp_zgrad_scattered: no finished scattered step");
         return VGGP_ESTATE;
@@ -785,6 +796,11 @@ extern "C" int vggp_zgrad_scattered(vggp_ctx* c, const double* y, double* gz1, d
 
 // q(v) of the last masked step: mean = (s1 s2 / v) L1 A0 L2^T, diag cov = s1 s2 rowdot((L1 (x) L2) Sinv, L1 (x) L2)
 extern "C" int vggp_qv_masked(vggp_ctx* c, double* mean, double* var, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_qv(c, mean, var, stream ? (hipStream_t)stream : c->own_stream);
+    }
     if (!c || !c->have_masked || !c->masked) { vg_set_error("vggp_qv_masked: no finished masked step"); return VGGP_ESTATE; }
     VG_REQUIRE(mean && var, "vggp_qv_masked: null output");
     VG_ENTER_DEVICE(c->device);
@@ -857,6 +873,11 @@ __global__ void vgm_readout_kernel(const double* T, const double* ST, const doub
 // with the cross-covariances in place of the kernel columns and kd1_a kd2_b in place of the unit prior variance.
 extern "C" int vggp_readout_masked(vggp_ctx* c, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1,
                                    const double* kd2, double* mean, double* var, int flags, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_readout(c, C1, mv1, C2, mv2, kd1, kd2, mean, var, flags, stream ? (hipStream_t)stream : c->own_stream);
+    }
     if (!c || !c->have_masked || !c->masked) { vg_set_error("vggp_readout_masked: no finished masked / scattered step"); return VGGP_ESTATE; }
     VG_REQUIRE(C1 && C2 && kd1 && kd2 && mean && var && mv1 > 0 && mv2 > 0, "vggp_readout_masked: bad argument");
     VG_ENTER_DEVICE(c->device);
@@ -895,6 +916,11 @@ extern "C" int vggp_readout_masked(vggp_ctx* c, const double* C1, int64_t mv1, c
 //   t = (L1^{-1} a1(x*)) (x) (L2^{-1} a2(x*)),  mean = rho t^T a0,  var = s1 s2 (1 - |t|^2 + t^T Sigma~^{-1} t)
 extern "C" int vggp_posterior_masked(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var,
                                      void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_posterior(c, xs1, xs2, ns, mean, var, stream ? (hipStream_t)stream : c->own_stream);
+    }
     if (!c || !c->have_masked || !c->masked) { vg_set_error("vggp_posterior_masked: no finished masked step"); return VGGP_ESTATE; }
     VG_REQUIRE(xs1 && xs2 && mean && var && ns >= 0, "vggp_posterior_masked: bad argument");
     if (ns == 0) return VGGP_OK;
@@ -936,6 +962,11 @@ hipError_t vg_prior_cov_launch(const double* xs1, const double* xs2, long ns, in
 
 // dense covariance of posterior(x*) of the last masked step: cov = K** + s1 s2 (T^T Sigma~^{-1} T - T^T T), T = (L1^{-1} a1*) (x) (L2^{-1} a2*)
 extern "C" int vggp_posterior_cov_masked(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* cov, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_posterior_cov(c, xs1, xs2, ns, cov, stream ? (hipStream_t)stream : c->own_stream);
+    }
     if (!c || !c->have_masked || !c->masked) { vg_set_error("vggp_posterior_cov_masked: no finished masked step"); return VGGP_ESTATE; }
     VG_REQUIRE(xs1 && xs2 && cov && ns >= 1, "vggp_posterior_cov_masked: bad argument");
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
@@ -977,6 +1008,11 @@ __global__ void vgm_scale_e_kernel(double* x, long n, const double* theta, int e
     if (i < n) x[i] *= (e1 > 0 ? theta[2] : 1.0 / theta[2]) * (e2 > 0 ? theta[3] : 1.0 / theta[3]);
 }
 extern "C" int vggp_qv_cov_masked(vggp_ctx* c, double* cov, void* stream) {
+    if (c && c->is_paired) {
+        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
+        VG_ENTER_DEVICE(c->device);
+        return vg_paired_qv_cov(c, cov, stream ? (hipStream_t)stream : c->own_stream);
+    }
     if (!c || !c->have_masked || !c->masked) { vg_set_error("vggp_qv_cov_masked: no finished masked step"); return VGGP_ESTATE; }
     VG_REQUIRE(cov, "vggp_qv_cov_masked: null output");
     VG_ENTER_DEVICE(c->device);
@@ -1343,6 +1379,7 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
 extern "C" int vggp_elbo_step_masked_iter(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs, const double theta[5],
                                           int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5], vggp_info* info,
                                           void* stream) {
+    VG_NOT_PAIRED(c, "vggp_elbo_step_masked_iter");
     int rc = masked_iter_once(c, Ym, W, n_obs, yy_obs, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
     if (rc == VGI_ESTALE) rc = masked_iter_once(c, Ym, W, n_obs, yy_obs, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
     if (rc == VGI_ESTALE) { vg_set_error("vggp_elbo_step_masked_iter: internal (stale basis after a cold solve)"); rc = VGGP_ESTATE; }

@@ -80,6 +80,7 @@ class Engine:
         self.m1 = self.m2 = self.n1 = self.n2 = 0
         self.planned = False
         self._step_bufs = None
+        self.paired = False          # the current plan is a paired one (plan_paired)
         self.plan_token = 0          # bumped by every plan(): a model sharing this engine re-plans when it is not the last planner
 
     @staticmethod
@@ -143,8 +144,36 @@ class Engine:
         self.scattered = bool(scattered)
         with torch.cuda.device(self.device):
             check(self.lib.vggp_plan(self._h, C.byref(d)))
+        self.paired = False
         self.m1, self.m2, self.n1, self.n2 = m1, m2, len(x1), len(x2)
         self.payload_len = int(self.lib.vggp_payload_len(self._h))
+        self.planned = True
+        self.plan_token += 1
+
+    def plan_paired(self, kind: str, Z, x1, x2, scattered: bool = False) -> None:
+        """Paired (general) inducing points (VGGP_FLAG_PAIRED_Z): Z (M, 2) any set of points, Kuu = s (K1 o K2).  x1, x2: the grid
+        axes of Y [n2, n1], or (scattered=True) the coordinates of the N points.  The steps, zgrad*, set_inducing, qv_masked,
+        qv_cov_masked, readout(masked=True) and posterior_masked / posterior_cov(masked=True) then mean the paired model."""
+        Zn = np.ascontiguousarray(np.asarray(Z, dtype=np.float64).reshape(-1, 2))
+        z1, z2 = np.ascontiguousarray(Zn[:, 0]), np.ascontiguousarray(Zn[:, 1])
+        x1, x2 = _dvec(x1), _dvec(x2)
+        if scattered and len(x1) != len(x2):
+            raise ValueError("scattered plan: x1 and x2 must hold one coordinate pair per point")
+        M = Zn.shape[0]
+        d = Desc()
+        d.kind1 = d.kind2 = KIND[kind]
+        d.basis1 = d.basis2 = BASIS["points"]
+        d.n1, d.n2, d.m1, d.m2 = len(x1), len(x2), M, M
+        d.n_total = len(x1) if scattered else len(x1) * len(x2)
+        d.x1, d.x2, d.grid1, d.grid2 = x1.ctypes.data, x2.ctypes.data, z1.ctypes.data, z2.ctypes.data
+        d.warm_start = 0
+        d.flags = _lib.FLAG_PAIRED_Z | (_lib.FLAG_SCATTERED if scattered else 0)
+        with torch.cuda.device(self.device):
+            check(self.lib.vggp_plan(self._h, C.byref(d)))
+        self.scattered = bool(scattered)
+        self.paired = True
+        self.m1, self.m2, self.n1, self.n2 = M, M, len(x1), len(x2)
+        self.payload_len = 0
         self.planned = True
         self.plan_token += 1
 
@@ -209,7 +238,9 @@ class Engine:
         return elbo.value, np.array(list(grad)), self._info(info)
 
     def qv_masked(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        mean = torch.empty(self.m1, self.m2, dtype=torch.float64, device=self.device)
+        """-> mean, var [m1, m2]; on a paired plan q(u) over the M inducing points, [M] each."""
+        shape = (self.m1,) if self.paired else (self.m1, self.m2)
+        mean = torch.empty(*shape, dtype=torch.float64, device=self.device)
         var = torch.empty_like(mean)
         check(self.lib.vggp_qv_masked(self._h, _ptr(mean), _ptr(var), _stream(self.device)))
         return mean, var
@@ -297,7 +328,7 @@ class Engine:
         return g1, g2
 
     def qv_cov_masked(self) -> torch.Tensor:
-        M = self.m1 * self.m2
+        M = self.m1 if self.paired else self.m1 * self.m2
         cov = torch.empty(M, M, dtype=torch.float64, device=self.device)
         check(self.lib.vggp_qv_cov_masked(self._h, _ptr(cov), _stream(self.device)))
         return cov

@@ -780,28 +780,104 @@ class univariate:
 
 class GriddedMatern12SVGP(_GriddedReadout, KroneckerStructure):
     """gridded_kronecker_structure.py:222-460: inducing POINTS Z (M, 2) with a gridded read-out on B0 cells.  The reference
-    evaluates the product kernel on the rows of Z (Kuu = k(Z, Z), :252-264): that is a Kronecker product exactly when Z is the
-    cartesian product of its per-dimension coordinates, which is the case this engine covers -- Z must list
-    cartesian_prod(z1, z2) (either coordinate fastest); arbitrary scattered Z has no per-dimension factors."""
+    evaluates the product kernel on the rows of Z (Kuu = k(Z, Z), :252-264), a Hadamard product K1 o K2.
 
-    def __init__(self, X, y, Z: torch.Tensor, n_b0_splines: int, dim1_grid_lims, dim2_grid_lims, **kw):
+    inducing="grid": Z lists cartesian_prod(z1, z2) (either coordinate fastest), k(Z, Z) = kron(K1, K2) and the Kronecker engine
+    runs; Z stays frozen.  inducing="general": any Z (notebooks 5, 6, 61, 7 draw it at random) through the paired inducing points of
+    the engine (VGGP_FLAG_PAIRED_Z, dense M-space, M <= 16384); Z is a trainable Parameter as in the reference (:236) unless
+    train_z=False, and `_elbo()` carries its analytic gradient.  inducing="auto" picks "grid" for a cartesian Z, "general" when no
+    coordinate column repeats a value, and raises otherwise (select_inducing_mode)."""
+
+    def __init__(self, X, y, Z: torch.Tensor, n_b0_splines: int, dim1_grid_lims, dim2_grid_lims, inducing: str = "auto",
+                 train_z: bool = True, **kw):
         KroneckerStructure.__init__(self, X, y, **kw)
         Zt = torch.as_tensor(Z, dtype=torch.float64)
-        self.Z = torch.nn.Parameter(Zt.clone(), requires_grad=False)
-        self._z1, self._z2, self._u_of_row = _detect_cartesian(Zt)
+        self.inducing = select_inducing_mode(Zt, inducing)
+        if self.inducing == "grid":
+            self.Z = torch.nn.Parameter(Zt.clone(), requires_grad=False)
+            self._z1, self._z2, self._u_of_row = _detect_cartesian(Zt)
+        else:
+            self.Z = torch.nn.Parameter(Zt.clone(), requires_grad=bool(train_z))
+            if self._masked:                                    # a grid with holes is its observed points
+                self._as_scattered()
+            self._masked = True                                 # read-outs: the dense M-space ones (vggp_*_masked)
         self._grid_init(n_b0_splines, dim1_grid_lims, dim2_grid_lims)
 
     def _basis(self):
+        if self.inducing == "general":
+            Z = self.Z.detach().cpu().numpy()
+            return "paired", Z[:, 0].copy(), Z[:, 1].copy()
         return "points", self._z1.copy(), self._z2.copy()
 
+    def _plan(self):
+        if self.inducing == "grid":
+            return KroneckerStructure._plan(self)
+        _, g1, g2 = self._basis()
+        key = ("paired", g1.tobytes(), g2.tobytes())
+        if self._planned and self._plan_token == self._engine.plan_token and self._plan_key is not None:
+            if key != self._plan_key:              # only Z moved (an optimiser step): new coordinates in place, no re-plan
+                if key[1] != self._plan_key[1]:
+                    self._engine.set_inducing(0, g1)
+                if key[2] != self._plan_key[2]:
+                    self._engine.set_inducing(1, g2)
+                self._plan_key = key
+            return
+        self._engine.plan_paired(self.kind, np.stack([g1, g2], axis=1), self._x1, self._x2, scattered=self._scattered)
+        self._planned = True
+        self._plan_token, self._plan_key = self._engine.plan_token, key
+
+    def _engine_step(self, theta):
+        if self.inducing == "grid":
+            return KroneckerStructure._engine_step(self, theta)
+        self._plan()
+        if self._scattered:
+            return self._engine.elbo_step_scattered(self._Y, self._yy, theta)
+        return self._engine.elbo_step(self._Y, self._yy, theta)
+
+    def _elbo(self) -> torch.Tensor:
+        if self.inducing == "general":
+            return _ElboFunction.apply(self._theta(), self, self.Z)
+        return KroneckerStructure._elbo(self)
+
     def _cross(self, d: int, ell: float) -> torch.Tensor:
-        return _b0_cross_points(self.b0_mesh_1 if d == 0 else self.b0_mesh_2, torch.as_tensor(self._z1 if d == 0 else self._z2), ell)
+        mesh = self.b0_mesh_1 if d == 0 else self.b0_mesh_2
+        if self.inducing == "general":
+            return _b0_cross_points(mesh, self.Z.detach()[:, d].cpu(), ell)
+        return _b0_cross_points(mesh, torch.as_tensor(self._z1 if d == 0 else self._z2), ell)
 
     def q_u(self) -> MultivariateNormal:
         """:396-405, in the row order of the caller's Z."""
         qu = KroneckerStructure.q_v(self)
+        if self.inducing == "general":
+            return qu
         idx = torch.as_tensor(self._u_of_row)
         return MultivariateNormal(qu.mean[idx], qu.variance[idx])
+
+
+def select_inducing_mode(Z, inducing: str = "auto", rtol: float = 1e-6) -> str:
+    """How GriddedMatern12SVGP treats Z (M, 2): "grid" (a full cartesian grid, Kronecker engine) or "general" (paired inducing
+    points).  "auto": "grid" when Z is cartesian, "general" when neither coordinate column repeats a value (up to rtol of its span,
+    as _cluster_coordinates judges it), otherwise ValueError -- a cartesian grid with a dropped row is almost certainly a mistake."""
+    if inducing not in ("auto", "grid", "general"):
+        raise ValueError(f"inducing must be 'auto', 'grid' or 'general', got {inducing!r}")
+    Zt = torch.as_tensor(Z, dtype=torch.float64)
+    if Zt.dim() != 2 or Zt.shape[1] != 2:
+        raise ValueError("Z must be (M, 2)")
+    if inducing == "general":
+        return "general"
+    try:
+        _detect_cartesian(Zt, rtol)
+        return "grid"
+    except ValueError:
+        if inducing == "grid":
+            raise
+    Zn = Zt.detach().cpu().numpy()
+    z1, _ = _cluster_coordinates(Zn[:, 0], rtol)
+    z2, _ = _cluster_coordinates(Zn[:, 1], rtol)
+    if len(z1) == Zn.shape[0] and len(z2) == Zn.shape[0]:
+        return "general"
+    _detect_cartesian(Zt, rtol, hint=True)
+    raise AssertionError("unreachable")
 
 
 def _cluster_coordinates(v: np.ndarray, rtol: float):
@@ -818,7 +894,7 @@ def _cluster_coordinates(v: np.ndarray, rtol: float):
     return centres, inv
 
 
-def _detect_cartesian(Z: torch.Tensor, rtol: float = 1e-6):
+def _detect_cartesian(Z: torch.Tensor, rtol: float = 1e-6, hint: bool = False):
     """Z (M, 2) listing every pair of cartesian_prod(z1, z2) exactly once, in any row order -> (z1, z2, u_of_row) with
     u_of_row[r] = i1 * m2 + i2, the engine's inducing index of row r; raises when Z is not such a grid.  Coordinates are
     matched up to rtol of their span, so a grid that passed through float32 or a scaler is still recognised."""
@@ -830,7 +906,9 @@ def _detect_cartesian(Z: torch.Tensor, rtol: float = 1e-6):
     u = i1 * len(z2) + i2
     if len(z1) * len(z2) != Zn.shape[0] or len(np.unique(u)) != Zn.shape[0]:
         raise ValueError("GriddedMatern12SVGP: Z must be a full cartesian grid cartesian_prod(z1, z2): only then is "
-                         "k(Z, Z) = kron(K1, K2) (arbitrary scattered inducing points are out of scope)")
+                         "k(Z, Z) = kron(K1, K2)" + ("; a Z whose coordinates repeat but that is no full grid is refused by "
+                         "inducing='auto' -- pass inducing=\"general\" to use arbitrary inducing points" if hint else
+                         " (inducing=\"general\" takes arbitrary inducing points)"))
     return z1, z2, u
 
 
