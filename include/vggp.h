@@ -194,10 +194,37 @@ int vggp_elbo_step_masked(vggp_ctx* ctx, const double* Ym, const double* W, doub
  * probe estimator.  Bitwise reproducible.  Stated tolerance against vggp_elbo_step_masked: ELBO 1e-5 relative, gradient 1e-4 of
  * its largest component (n_probes = 16).  n_probes <= 0: 16; tol <= 0: 1e-10 (PCG residual, relative); max_iter <= 0: 100.
  * Arguments otherwise as vggp_elbo_step_masked; single-rank contexts; info->rounds1 = PCG iterations, info->sweeps1 = probes.
- * The dense read-outs (vggp_qv_masked, ...) need the dense step. */
+ * Its read-outs are vggp_qv_masked_iter and vggp_posterior_masked_iter below (the dense ones, vggp_qv_masked, ..., return
+ * VGGP_ESTATE after this step: there is no Sigma~^-1 to read). */
 int vggp_elbo_step_masked_iter(vggp_ctx* ctx, const double* Ym, const double* W, double n_obs, double yy_obs,
                                const double theta[5], int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5],
                                vggp_info* info, void* stream);
+/* Read-outs of the iterative step, again without any M x M matrix.  Every read-out quantity belongs to a rank-one whitened
+ * column t = u1 (x) u2:  mean = (s1 s2 / sigma^2) t^T a0,  var = s1 s2 (kappa - |t|^2 + t^T Sigma~^-1 t), with a0 = Sigma~^-1 c0
+ * from the step and t^T Sigma~^-1 t from a block PCG solve Sigma~ X = T over `block` columns at a time: the step's operator, its
+ * preconditioner (in the eigenbasis the step left behind) and its per-column stopping rule |r| <= tol |r0|.  No probes: the
+ * results are deterministic.  Cost: ceil(columns / block) block solves, each about the step's PCG at the same width.
+ *   W, n_obs   the mask and observation count the step was given (DEVICE [n2][n1])
+ *   tol <= 0: 1e-10;  max_iter <= 0: 100;  block <= 0: the largest of 64, 32, 16, ... the step's index limits allow; block <= 64
+ *   info       (may be NULL) rounds1 = largest PCG iteration count over the block solves, sweeps1 = number of block solves
+ * Both return VGGP_ESTATE unless the LAST finished step on the context was a successful vggp_elbo_step_masked_iter (vggp_plan,
+ * vggp_set_inducing, any other step and a failed iterative step end that state); VGGP_ENOCONV when a column does not converge;
+ * VGGP_EINVAL on paired, scattered or multi-rank contexts, a cell index outside [0, M), block > 64.  The workspace (block
+ * vectors and one n1 x block x n2 field) is allocated on first use and apart from the step's: a read-out leaves the step's kept
+ * preconditioner basis valid and the next step's results unchanged.
+ *
+ * q(v): u_d = row i_d of L0_d, kappa = |t|^2, so var = s1^e1 s2^e2 t^T Sigma~^-1 t (e_d = -1 for VFF / B1 features, else 1); the
+ * mean needs no solve (L0_1 A0 L0_2^T, scaled as vggp_qv_masked scales it).
+ *   mean   DEVICE [m1][m2], all cells (NULL to skip)
+ *   cells  HOST int64 [n_cells] flat indices i1*m2 + i2, or NULL with n_cells = M for every cell
+ *   var    DEVICE [n_cells] (NULL with n_cells = 0: mean only) */
+int vggp_qv_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, const int64_t* cells, int64_t n_cells, double tol,
+                        int max_iter, int block, double* mean, double* var, vggp_info* info, void* stream);
+/* posterior(x*) (kronecker_structure.py:199-230 on the observed subset): u_d = L0_d^-1 a_d(x*_d), kappa = 1.
+ *   xs1, xs2 DEVICE [n_star];  mean, var DEVICE [n_star] */
+int vggp_posterior_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, const double* xs1, const double* xs2,
+                               int64_t n_star, double tol, int max_iter, int block, double* mean, double* var, vggp_info* info,
+                               void* stream);
 /* q(v) of the last masked step: mean and covariance diagonal, DEVICE [m1][m2]. */
 int vggp_qv_masked(vggp_ctx* ctx, double* mean, double* var, void* stream);
 /* posterior(x*) of the last masked step (kronecker_structure.py:199-230); arguments as vggp_posterior. */

@@ -320,7 +320,7 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
         c->planned = false;
         graphs_clear(c);
         VG_HIP(hipDeviceSynchronize());
-        c->have_partials = c->have_step = c->have_masked = false;
+        c->have_partials = c->have_step = c->have_masked = c->have_iter = false;
         c->acc_valid = false; c->last_payload = nullptr;
         c->is_paired = false;
         if ((rc = vg_paired_plan(c, desc))) return rc;
@@ -400,7 +400,7 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
     }
     VG_HIP(hipDeviceSynchronize());
     c->desc.x1 = c->desc.x2 = c->desc.grid1 = c->desc.grid2 = nullptr;   // host pointers not retained
-    c->have_partials = c->have_step = c->have_masked = false;
+    c->have_partials = c->have_step = c->have_masked = c->have_iter = false;
     vg_masked_new_plan(c);
     c->planned = true;
     return VGGP_OK;
@@ -425,7 +425,7 @@ extern "C" int vggp_set_inducing(vggp_ctx* c, int dim, const double* z, int64_t 
     VG_ENTER_DEVICE(c->device);
     VG_HIP(hipStreamSynchronize(c->own_stream));              // no step of this context is reading the old coordinates
     VG_HIP(hipMemcpy(d.grid, z, sizeof(double) * m, hipMemcpyHostToDevice));
-    c->have_step = false; c->have_partials = false; c->have_masked = false; c->acc_valid = false;      // read-outs need a new step
+    c->have_step = false; c->have_partials = false; c->have_masked = false; c->have_iter = false; c->acc_valid = false;      // read-outs need a new step
     return VGGP_OK;
 }
 
@@ -1642,6 +1642,7 @@ extern "C" int vggp_elbo_partials(vggp_ctx* c, const double* Y, const double the
     VG_NOT_PAIRED(c, "vggp_elbo_partials");
     if (!c || !c->planned) { vg_set_error("vggp_elbo_partials: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(Y && theta && payload, "vggp_elbo_partials: null argument");
+    c->have_iter = false;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     int rc = set_theta(c, theta);
@@ -1677,6 +1678,7 @@ static int elbo_finish_once(vggp_ctx* c, const double* payload, double yy_total,
                             double* elbo_out, double grad_out[5], vggp_info* info, void* stream) {
     if (!c || !c->planned || !c->have_partials) { vg_set_error("vggp_elbo_finish: call vggp_elbo_partials first"); return VGGP_ESTATE; }
     VG_REQUIRE(payload && theta && elbo_out && grad_out, "vggp_elbo_finish: null argument");
+    c->have_iter = false;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     int rc = set_theta(c, theta);
@@ -1755,6 +1757,7 @@ static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const d
     if (!c || !c->planned) { vg_set_error("vggp_elbo_step: context not planned"); return VGGP_ESTATE; }
     if (c->desc.flags & VGGP_FLAG_SCATTERED) { vg_set_error("vggp_elbo_step: the context was planned for scattered points (use vggp_elbo_step_scattered)"); return VGGP_ESTATE; }
     VG_REQUIRE(Y && theta && elbo_out && grad_out, "vggp_elbo_step: null argument");
+    c->have_iter = false;            // (the eigensolver chain overwrites the basis the iterative step's read-outs precondition with)
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     int rc = set_theta(c, theta);

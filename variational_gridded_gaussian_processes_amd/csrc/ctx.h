@@ -62,6 +62,7 @@ struct vggp_ctx {
     int gh_slabs[2] = {1, 1}, cc_slabs = 1;      // split-K slab counts actually produced by the last partials launch
     long payload_len = 0;
     bool have_partials = false, have_step = false, have_masked = false;
+    bool have_iter = false;          // the last finished step was a successful vggp_elbo_step_masked_iter (its read-outs: masked.hip)
     void* masked = nullptr;          // VgMasked workspace (masked.hip), allocated on first use
     void* paired = nullptr;          // VgPaired workspace (paired.hip): allocated by a plan with VGGP_FLAG_PAIRED_Z
     bool is_paired = false;          // the current plan is a paired one: only the entries listed in vggp.h apply

@@ -200,6 +200,8 @@ struct VgMasked {
     bool iter = false;             // iterative step (vggp_elbo_step_masked_iter): none of the M x M / pair-product buffers exist
     void* imem = nullptr;          // its own workspace (VgIter, below)
     size_t ibytes = 0;
+    void* rmem = nullptr;          // workspace of the iterative step's read-outs (VgReadout, below): apart from imem, so that a read-out
+    size_t rbytes = 0;             // leaves the kept preconditioner basis and everything else of the step where it is
     // the iterative step's kept preconditioner basis: valid, steps since the cold solve, PCG iterations right after it / last step
     bool ib_valid = false, ib_fresh = false;
     int ib_age = 0, ib_ref_its = 0, ib_last_its = 0, ib_nbc = 0, ib_maxit = 0;
@@ -258,6 +260,7 @@ static int vgm_prepare(vggp_ctx* c, bool iter = false) {
         return VGGP_OK;
     if (w->mem) { VG_HIP(hipFree(w->mem)); w->mem = nullptr; }
     if (w->imem) { VG_HIP(hipFree(w->imem)); w->imem = nullptr; w->ibytes = 0; }
+    if (w->rmem) { VG_HIP(hipFree(w->rmem)); w->rmem = nullptr; w->rbytes = 0; }
     w->ib_valid = false;
     w->M = m1 * m2; w->m1 = (int)m1; w->m2 = (int)m2; w->n1 = c->desc.n1; w->n2 = c->desc.n2; w->scattered = sc; w->iter = iter;
     w->nblk = (int)((w->M + VG_MB - 1) / VG_MB);
@@ -293,6 +296,7 @@ void vg_masked_free(vggp_ctx* c) {
     if (!w) return;
     if (w->mem) (void)hipFree(w->mem);
     if (w->imem) (void)hipFree(w->imem);
+    if (w->rmem) (void)hipFree(w->rmem);
     delete w;
     c->masked = nullptr;
 }
@@ -442,6 +446,7 @@ extern "C" int vggp_elbo_step_masked(vggp_ctx* c, const double* Ym, const double
     if (!c || !c->planned) { vg_set_error("vggp_elbo_step_masked: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(Ym && W && theta && elbo_out && grad_out, "vggp_elbo_step_masked: null argument");
     c->have_masked = false;          // a failed step must not leave an earlier step's state readable (qv_masked / posterior_masked)
+    c->have_iter = false;
     VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "vggp_elbo_step_masked: the context was planned for scattered points");
     const long m1 = c->desc.m1, m2 = c->desc.m2, n1 = c->desc.n1, n2 = c->desc.n2, M = m1 * m2;
     VG_REQUIRE(M <= VGM_MAX_M, "vggp_elbo_step_masked: M = m1*m2 = %ld too large for the dense masked solver (<= %d)", M, VGM_MAX_M);
@@ -1390,6 +1395,7 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     if (!c || !c->planned) { vg_set_error("vggp_elbo_step_masked_iter: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(Ym && W && theta && elbo_out && grad_out, "vggp_elbo_step_masked_iter: null argument");
     c->have_masked = false;
+    c->have_iter = false;            // ... and a failed iterative step leaves nothing for vggp_qv_masked_iter / vggp_posterior_masked_iter
     VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "vggp_elbo_step_masked_iter: the context was planned for scattered points");
     VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "vggp_elbo_step_masked_iter: single-rank contexts only");
     if (n_probes <= 0) n_probes = 16;
@@ -1618,5 +1624,252 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     if (w.ib_fresh) { w.ib_valid = true; w.ib_age = 0; w.ib_ref_its = iters; }
     w.ib_last_its = iters;
     c->have_step = false; c->have_partials = false;
+    c->have_iter = true;             // a0, the factors and the preconditioner's basis are there for the iterative read-outs
     return VGGP_OK;
+}
+
+// ================================================================================================================================
+// Read-outs of the iterative step: q(v) and posterior(x*) without Sigma~^-1 as a matrix (vggp_qv_masked_iter,
+// vggp_posterior_masked_iter).  The algebra is vggp_qv_masked's / vggp_posterior_masked's; every quantity belongs to a rank-one
+// whitened column t = u1 (x) u2:
+//     mean = (s1 s2 / v) t^T a0,      var = s1 s2 (kappa - |t|^2 + t^T Sigma~^-1 t)
+//   posterior(x*)   u_d = L0_d^-1 a_d(x*_d), kappa = 1
+//   q(v) at (i1,i2) u_d = row i_d of L0_d,  kappa = |t|^2  ->  var = s1^e1 s2^e2 t^T Sigma~^-1 t;  the mean of ALL cells is
+//                   L0_1 A0 L0_2^T (two GEMMs, no solve)
+// t^T Sigma~^-1 t comes from a block PCG solve Sigma~ X = T over `block` <= 64 columns at a time in the step's interleaved layout
+// [m1][nbc][m2], with the step's operator, its preconditioner (the basis and Rayleigh quotients it left in d.Qt, d.lam0) and its
+// per-column stopping rule.  No probes: deterministic.  Workspace of its own (w.rmem): the step's arena, with the kept
+// preconditioner basis Qk1/Qk2 in it, is not touched.  Specification: tests/masked_iter_readout_spec.py.
+// ================================================================================================================================
+struct VgReadout {
+    VgIter it;                  // the block vectors the step's helpers work on (Wz, alh, beh: one row each; the rest of VgIter unused)
+    double *T;                  // the right-hand sides, kept for the reductions
+    double *A1, *A2, *U1, *U2;  // posterior(x*): factor columns a_d(x*) and U_d = L0_d^-1 a_d  [m_d][cn]
+    long long* cells;           // q(v): this block's flat cell indices
+};
+
+// T[a][c][b] = U1[a][c] U2[b][c] for the cn columns of this block (U_d: [m_d][cn]); the unused columns of a ragged block are zero
+__global__ void vgi_rank1_kernel(const double* U1, const double* U2, int m1, int nbc, int m2, int cn, double* T) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)m1 * nbc * m2) return;
+    const int b = (int)(idx % m2), c = (int)((idx / m2) % nbc), a = (int)(idx / ((long)m2 * nbc));
+    T[idx] = c < cn ? U1[(long)a * cn + c] * U2[(long)b * cn + c] : 0.0;
+}
+// q(v): column c belongs to cell u = cells[c] (or u0 + c): T[a][c][b] = L0_1[i1][a] L0_2[i2][b], u = i1 m2 + i2
+__global__ void vgi_rank1_cells_kernel(const double* L1, const double* L2, const long long* cells, long u0, int m1, int nbc, int m2, int cn,
+                                       double* T) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)m1 * nbc * m2) return;
+    const int b = (int)(idx % m2), c = (int)((idx / m2) % nbc), a = (int)(idx / ((long)m2 * nbc));
+    if (c >= cn) { T[idx] = 0.0; return; }
+    const long u = cells ? (long)cells[c] : u0 + c;
+    const long i1 = u / m2, i2 = u - i1 * m2;
+    T[idx] = L1[i1 * m1 + a] * L2[i2 * m2 + b];
+}
+// one workgroup per column: lin = <T, a0>, nrm = <T, T>, quad = <T, X> in one pass, then the scaled outputs of the column.
+// mode 0 (posterior): mean = (s1 s2 / v) lin, var = s1 s2 (1 - nrm + quad);   mode 1 (q(v)): var = s1^e1 s2^e2 quad
+__global__ __launch_bounds__(256) void vgi_readout_reduce_kernel(const double* T, const double* X, const double* a0, int m1, int nbc, int m2,
+                                                                 const double* theta, int mode, int e1, int e2, double* mean, double* var) {
+    __shared__ double red[12];
+    const int c = blockIdx.x;
+    double lin = 0.0, nrm = 0.0, quad = 0.0;
+    for (long e = threadIdx.x; e < (long)m1 * m2; e += 256) {
+        const long a = e / m2, b = e - a * m2, o = (a * nbc + c) * m2 + b;
+        const double t = T[o];
+        lin += t * a0[e];
+        nrm += t * t;
+        quad += t * X[o];
+    }
+    for (int off = 32; off > 0; off >>= 1) { lin += __shfl_xor(lin, off); nrm += __shfl_xor(nrm, off); quad += __shfl_xor(quad, off); }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = lin; red[4 + (threadIdx.x >> 6)] = nrm; red[8 + (threadIdx.x >> 6)] = quad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        lin = (red[0] + red[1]) + (red[2] + red[3]);
+        nrm = (red[4] + red[5]) + (red[6] + red[7]);
+        quad = (red[8] + red[9]) + (red[10] + red[11]);
+        const double ss = theta[2] * theta[3];
+        if (mode == 0) {
+            mean[c] = (ss / theta[4]) * lin;
+            var[c] = ss * (1.0 - nrm + quad);
+        } else {
+            var[c] = (e1 > 0 ? theta[2] : 1.0 / theta[2]) * (e2 > 0 ? theta[3] : 1.0 / theta[3]) * quad;
+        }
+    }
+}
+
+static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post) {
+    const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M, mx = std::max(m1, m2);
+    size_t off = 0;
+    char* base = nullptr;
+    VgIter& it = r.it;
+    for (int pass = 0; pass < 2; ++pass) {
+        off = 0;
+        auto take = [&](size_t count) {
+            off = (off + 255) & ~size_t(255);
+            double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
+            off += count * sizeof(double);
+            return p;
+        };
+        it.Wt = take(n1 * n2);
+        it.X = take(M * nbc); it.R = take(M * nbc); it.Zp = take(M * nbc); it.Pd = take(M * nbc); it.AP = take(M * nbc);
+        it.Tm = take(M * nbc); it.Tm2 = take(M * nbc); r.T = take(M * nbc);
+        it.T1 = take(n1 * nbc * mx);
+        it.F0 = take(n1 * nbc * n2);
+        it.alh = take((size_t)nbc); it.beh = take((size_t)nbc);
+        it.col = take(8 * (size_t)nbc);
+        r.A1 = take(post ? m1 * nbc : 0); r.A2 = take(post ? m2 * nbc : 0);
+        r.U1 = take(post ? m1 * nbc : 0); r.U2 = take(post ? m2 * nbc : 0);
+        r.cells = reinterpret_cast<long long*>(take((size_t)nbc));
+        it.nact = reinterpret_cast<int*>(take(8));
+        if (pass == 0) {
+            const size_t need = off + 4096;
+            if (w.rbytes < need) {
+                if (w.rmem) { VG_HIP(hipFree(w.rmem)); w.rmem = nullptr; w.rbytes = 0; }
+                size_t free_b = 0, total_b = 0;
+                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
+                    vg_set_error("the read-out workspace of the iterative masked step needs %.1f GiB at block = %d but only %.1f GiB of device "
+                                 "memory are free (a smaller block needs less)", (double)need / 1073741824.0, nbc, (double)free_b / 1073741824.0);
+                    return VGGP_ENOMEM;
+                }
+                VG_HIP(hipMalloc(&w.rmem, need));
+                w.rbytes = need;
+            }
+            base = reinterpret_cast<char*>(w.rmem);
+        }
+    }
+    it.nbc = nbc; it.maxit = 1;
+    return VGGP_OK;
+}
+
+// Sigma~ X = T for the block in r.T: the step's PCG loop without the coefficient history (zero columns start inactive)
+static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, double tol, int max_iter, int* iters_out, int* nact_out,
+                             hipStream_t st) {
+    VgIter& it = r.it;
+    const long m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M;
+    const int nbc = it.nbc;
+    const long nb = M * nbc;
+    const double *B1 = c->d[0].BV, *B2 = c->d[1].BV;
+    int rc;
+    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
+    VG_HIP(hipMemcpyAsync(it.R, r.T, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
+    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col, it.col + 3 * nbc);
+    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
+    int iters = 0, nact = nbc;
+    for (int k = 0; k < max_iter && nact > 0; ++k) {
+        if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
+        VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
+        if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
+        VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
+        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
+                           (int)m2, it.col + nbc, (double*)nullptr);
+        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, 0, tol, it.alh, it.beh, it.nact);
+        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 1);
+        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
+        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col + 5 * nbc,
+                           it.col + 3 * nbc);
+        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, 0, tol, it.alh, it.beh, it.nact);
+        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 2);
+        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipStreamSynchronize(st));
+        nact = c->h_out->counters[0][0];
+        iters = k + 1;
+    }
+    *iters_out = iters;
+    *nact_out = nact;
+    return VGGP_OK;
+}
+
+// mode 0: posterior at (xs1, xs2)[ncols];  mode 1: q(v) variance at cells[ncols] (host; null: every cell) and the mean of all cells
+static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, const double* W, double n_obs, const int64_t* cells, const double* xs1,
+                           const double* xs2, int64_t ncols, double tol, int max_iter, int block, double* mean, double* var, vggp_info* info,
+                           void* stream) {
+    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
+    VG_NOT_PAIRED(c, fn);
+    VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: the context was planned for scattered points", fn);
+    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
+    const long m1 = c->desc.m1, m2 = c->desc.m2, n1 = c->desc.n1, n2 = c->desc.n2, M = m1 * m2;
+    VG_REQUIRE(W && ncols >= 0 && std::isfinite(n_obs) && n_obs > 0.0, "%s: bad argument", fn);
+    VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
+    if (mode == 0) VG_REQUIRE(xs1 && xs2 && mean && var, "%s: null argument", fn);
+    else {
+        VG_REQUIRE((ncols == 0 && !var) || (ncols > 0 && var), "%s: var and n_cells must be given together (NULL with 0: mean only)", fn);
+        VG_REQUIRE(cells || ncols == 0 || ncols == M, "%s: cells = NULL means every cell: n_cells must be M = %ld", fn, M);
+        if (cells)
+            for (int64_t k = 0; k < ncols; ++k)
+                VG_REQUIRE(cells[k] >= 0 && cells[k] < M, "%s: cells[%lld] = %lld is outside [0, M = %ld)", fn, (long long)k, (long long)cells[k], M);
+    }
+    auto fits = [&](long b) { return n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31); };
+    if (block <= 0) { block = 64; while (block > 1 && !fits(block)) block >>= 1; }
+    VG_REQUIRE(fits(block), "%s: problem too large for block = %d", fn, block);
+    if (!c->have_iter || !c->masked) { vg_set_error("%s: no finished vggp_elbo_step_masked_iter on this context", fn); return VGGP_ESTATE; }
+    if (max_iter <= 0) max_iter = 100;
+    if (!(tol > 0.0)) tol = 1e-10;
+    if (info) { info->jitter1 = info->jitter2 = 0.0; info->sweeps1 = info->sweeps2 = info->rounds1 = info->rounds2 = 0; info->status = 0; info->polished = 0; }
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    int rc;
+    const int e1 = (d1.basis == VGGP_BASIS_VFF || d1.basis == VGGP_BASIS_B1) ? -1 : 1;
+    const int e2 = (d2.basis == VGGP_BASIS_VFF || d2.basis == VGGP_BASIS_B1) ? -1 : 1;
+    if (mode == 1 && mean) {          // the mean of every cell: L0_1 A0 L0_2^T, scaled as vggp_qv_masked scales it
+        if ((rc = gemm1(d1.L0, m1, 1, w.a0, m2, 1, w.MkA1, (int)m2, (int)m1, (int)m2, (int)m1, st))) return rc;
+        if ((rc = gemm1(w.MkA1, m2, 1, d2.L0, 1, m2, mean, (int)m2, (int)m1, (int)m2, (int)m2, st))) return rc;
+        VGM_LAUNCH1D(vgm_scale_rho_kernel, M, st, mean, M, c->theta, e1, e2);
+        VG_HIP(hipGetLastError());
+    }
+    if (ncols == 0) { VG_HIP(hipStreamSynchronize(st)); return VGGP_OK; }
+    const int nbc = (int)std::min<int64_t>(block, ncols);
+    VgReadout r;
+    if ((rc = vgi_readout_prepare(w, r, nbc, mode == 0))) return rc;
+    VgIter& it = r.it;
+    hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
+    const double p = n_obs / ((double)n1 * (double)n2);
+    const long nb = M * nbc;
+    int max_its = 0, solves = 0;
+    for (int64_t off = 0; off < ncols; off += nbc) {
+        const int cn = (int)std::min<int64_t>(nbc, ncols - off);
+        if (mode == 0) {
+            VgFactorJob fj[2] = {
+                VgFactorJob{xs1 + off, d1.grid, r.A1, nullptr, nullptr, nullptr, cn, d1.m, d1.kind, d1.basis, 0, 0.0, c->desc.flags},
+                VgFactorJob{xs2 + off, d2.grid, r.A2, nullptr, nullptr, nullptr, cn, d2.m, d2.kind, d2.basis, 1, 0.0, c->desc.flags}};
+            VG_HIP(vg_factor_build_launch(fj, 2, c->theta, st));
+            VgGemmBatch g;
+            vg_gemm_init(&g);
+            vg_gemm_add(&g, d1.Linv0, m1, 1, r.A1, cn, 1, r.U1, cn, (int)m1, cn, (int)m1);
+            vg_gemm_add(&g, d2.Linv0, m2, 1, r.A2, cn, 1, r.U2, cn, (int)m2, cn, (int)m2);
+            VG_HIP(vg_gemm_launch(&g, st));
+            VGM_LAUNCH1D(vgi_rank1_kernel, nb, st, r.U1, r.U2, (int)m1, nbc, (int)m2, cn, r.T);
+        } else {
+            if (cells) VG_HIP(hipMemcpyAsync(r.cells, cells + off, sizeof(long long) * cn, hipMemcpyHostToDevice, st));
+            VGM_LAUNCH1D(vgi_rank1_cells_kernel, nb, st, d1.L0, d2.L0, cells ? r.cells : (const long long*)nullptr, (long)off, (int)m1, nbc, (int)m2,
+                         cn, r.T);
+        }
+        int iters = 0, nact = 0;
+        if ((rc = vgi_readout_solve(c, w, r, p, tol, max_iter, &iters, &nact, st))) return rc;
+        ++solves;
+        max_its = std::max(max_its, iters);
+        if (info) { info->rounds1 = max_its; info->sweeps1 = solves; }
+        if (nact > 0) {
+            vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left, block solve %d)", fn, tol, max_iter, nact, solves);
+            return VGGP_ENOCONV;
+        }
+        hipLaunchKernelGGL(vgi_readout_reduce_kernel, dim3(cn), dim3(256), 0, st, r.T, it.X, w.a0, (int)m1, nbc, (int)m2, c->theta, mode, e1, e2,
+                           mode == 0 ? mean + off : (double*)nullptr, var + off);
+    }
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+extern "C" int vggp_qv_masked_iter(vggp_ctx* c, const double* W, double n_obs, const int64_t* cells, int64_t n_cells, double tol, int max_iter,
+                                   int block, double* mean, double* var, vggp_info* info, void* stream) {
+    return vgi_readout_run(c, "vggp_qv_masked_iter", 1, W, n_obs, cells, nullptr, nullptr, n_cells, tol, max_iter, block, mean, var, info, stream);
+}
+
+extern "C" int vggp_posterior_masked_iter(vggp_ctx* c, const double* W, double n_obs, const double* xs1, const double* xs2, int64_t ns,
+                                          double tol, int max_iter, int block, double* mean, double* var, vggp_info* info, void* stream) {
+    return vgi_readout_run(c, "vggp_posterior_masked_iter", 0, W, n_obs, nullptr, xs1, xs2, ns, tol, max_iter, block, mean, var, info, stream);
 }

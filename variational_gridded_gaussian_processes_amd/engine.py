@@ -224,6 +224,42 @@ class Engine:
                                                   int(max_iter), C.byref(elbo), grad, C.byref(info), _stream(self.device)))
         return elbo.value, np.array(list(grad)), self._info(info)
 
+    def qv_masked_iter(self, W: torch.Tensor, n_obs: float, cells=None, variance: bool = True, tol: float = 1e-10,
+                       max_iter: int = 100, block: int = 0):
+        """q(v) after elbo_step_masked_iter (W, n_obs: the step's): -> (mean [m1, m2], var [n_cells] or None, info).  cells: flat
+        indices i1*m2 + i2 of the cells whose variance is wanted (None: every cell -- ceil(M / block) block PCG solves);
+        variance=False: the mean only (no solve).  info['rounds'][0] = most PCG iterations of a block solve, info['sweeps'][0] =
+        block solves."""
+        self._check_Y(W)
+        mean = torch.empty(self.m1, self.m2, dtype=torch.float64, device=self.device)
+        info = Info()
+        if not variance:
+            cp, nc, var = None, 0, None
+        elif cells is None:
+            cp, nc = None, self.m1 * self.m2
+            var = torch.empty(nc, dtype=torch.float64, device=self.device)
+        else:
+            ca = np.ascontiguousarray(torch.as_tensor(cells).detach().cpu().numpy().reshape(-1), dtype=np.int64)
+            cp, nc = ca.ctypes.data_as(C.POINTER(C.c_int64)), len(ca)
+            var = torch.empty(nc, dtype=torch.float64, device=self.device) if nc else None
+        check(self.lib.vggp_qv_masked_iter(self._h, _ptr(W), float(n_obs), cp, nc, float(tol), int(max_iter), int(block), _ptr(mean),
+                                           _ptr(var), C.byref(info), _stream(self.device)))
+        return mean, var, self._info(info)
+
+    def posterior_masked_iter(self, x_star: torch.Tensor, W: torch.Tensor, n_obs: float, tol: float = 1e-10, max_iter: int = 100,
+                              block: int = 0):
+        """posterior(x*) after elbo_step_masked_iter; x_star [ns, 2] -> (mean [ns], var [ns], info)."""
+        self._check_Y(W)
+        xs = x_star.to(self.device, torch.float64)
+        xs1, xs2 = xs[:, 0].contiguous(), xs[:, 1].contiguous()
+        ns = xs1.shape[0]
+        mean = torch.empty(ns, dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mean)
+        info = Info()
+        check(self.lib.vggp_posterior_masked_iter(self._h, _ptr(W), float(n_obs), _ptr(xs1), _ptr(xs2), ns, float(tol), int(max_iter),
+                                                  int(block), _ptr(mean), _ptr(var), C.byref(info), _stream(self.device)))
+        return mean, var, self._info(info)
+
     def elbo_step_scattered(self, y: torch.Tensor, yy: float, theta: Sequence[float]):
         """N scattered points (plan(..., scattered=True) with their coordinate pairs): y [N] float64 GPU tensor, yy = sum y^2;
         -> (elbo, grad[5], info).  qv_masked / posterior_masked / the *_cov_masked read-outs apply afterwards."""

@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import VggpError
 from .basis import B0SplineBasis, B1SplineBasis, FourierBasisMatern12
-from .engine import Engine
+from .engine import Engine, _basis_m
 
 NOISE_LOWER = 1e-4
 
@@ -98,9 +98,11 @@ class GaussianLikelihood(torch.nn.Module):
 
 class MultivariateNormal:
     """What q_v()/posterior() return: `.mean`, `.variance`, `.stddev`, `.confidence_region()` and a lazily
-    materialised `.covariance_matrix` (dense, small problems only)."""
+    materialised `.covariance_matrix` (dense, small problems only).  `variance` may be a callable: it is then evaluated once, on
+    the first use of `.variance`, `.stddev` or `.confidence_region()` (the all-cell variance of the iterative masked solver costs
+    M / 64 block solves, the mean none)."""
 
-    def __init__(self, mean: torch.Tensor, variance: torch.Tensor, cov_fn=None):
+    def __init__(self, mean: torch.Tensor, variance, cov_fn=None):
         self.mean = mean
         self._variance = variance
         self._cov_fn = cov_fn
@@ -108,11 +110,13 @@ class MultivariateNormal:
 
     @property
     def variance(self) -> torch.Tensor:
+        if callable(self._variance):
+            self._variance = self._variance()
         return self._variance
 
     @property
     def stddev(self) -> torch.Tensor:
-        return self._variance.clamp_min(0).sqrt()
+        return self.variance.clamp_min(0).sqrt()
 
     @property
     def covariance_matrix(self) -> torch.Tensor:
@@ -191,8 +195,18 @@ class KroneckerStructure(torch.nn.Module):
 
     kind = "matern12"
 
-    def __init__(self, X: torch.Tensor, y: torch.Tensor, engine: Optional[Engine] = None, warm_start: bool = True):
+    def __init__(self, X: torch.Tensor, y: torch.Tensor, engine: Optional[Engine] = None, warm_start: bool = True,
+                 solver: str = "auto"):
+        """solver: how a grid with holes is solved.  "dense": the M x M solver (M = m1 m2 <= 16384); "iterative": PCG without any
+        M x M matrix (Engine.elbo_step_masked_iter and its read-outs; also accepted on a full grid, which it treats as a mask of
+        ones); "auto": iterative only for a grid with holes whose M exceeds the dense solver's limit, dense everywhere else.
+        Scattered points and paired inducing points have no iterative solver: "iterative" raises ValueError there."""
         super().__init__()
+        if solver not in ("auto", "dense", "iterative"):
+            raise ValueError(f"solver must be 'auto', 'dense' or 'iterative', got {solver!r}")
+        self.solver = solver
+        self.n_probes, self.tol, self.max_iter = 16, 1e-10, 100      # of the iterative solver (the engine's defaults)
+        self._iter = False
         self.train_inputs = (X,)
         self.train_targets = y
         self.likelihood = GaussianLikelihood()
@@ -219,13 +233,30 @@ class KroneckerStructure(torch.nn.Module):
             self._nobs = float(W.sum())
         else:
             self._Y = yd.reshape(n2, n1).contiguous()
+            if solver == "iterative":    # a full grid through the iterative solver: a mask of ones
+                self._masked, self._nobs = True, float(n1 * n2)
+                self._W = torch.ones(n2, n1, dtype=torch.float64, device=self._engine.device)
+        if self._scattered:
+            self._no_iterative("scattered points")
         self._yy = float((yd * yd).sum().item()) if self._scattered else self._engine.sumsq(self._Y)
+
+    def _no_iterative(self, what: str):
+        if self.solver == "iterative":
+            raise ValueError(f"{type(self).__name__}: solver='iterative' needs observations on a grid (with or without holes); "
+                             f"{what} take the dense M-space solver")
+
+    def _use_iterative(self, basis, g1, g2) -> bool:
+        """The iterative masked solver applies (see __init__)."""
+        if self.solver == "dense" or self._scattered or not self._masked or basis == "paired":
+            return False
+        return self.solver == "iterative" or _basis_m(basis, np.asarray(g1)) * _basis_m(basis, np.asarray(g2)) > 16384
 
     def _as_scattered(self):
         """Switch a masked-grid model to the scattered representation of the same observations (one coordinate pair per point):
         the step with a Z-gradient on incomplete data is vggp_zgrad_scattered."""
         if self._scattered or not self._masked:
             return
+        self._no_iterative("a grid with holes whose inducing points are trained (it is treated as its observed points)")
         Xn = self.train_inputs[0].detach().cpu().numpy().astype(np.float64)
         yd = torch.as_tensor(self.train_targets, dtype=torch.float64).reshape(-1).to(self._engine.device)
         self._x1, self._x2 = Xn[:, 0].copy(), Xn[:, 1].copy()
@@ -247,6 +278,7 @@ class KroneckerStructure(torch.nn.Module):
         """(Re)plan the engine when this model is not its last planner (an Engine may be shared between models: the plan --
         factors, basis, meshes -- lives in the engine) or when its inducing description changed since the last plan."""
         basis, g1, g2 = self._basis()
+        self._iter = self._use_iterative(basis, g1, g2)
         key = (basis, np.asarray(g1).tobytes(), np.asarray(g2).tobytes())
         if self._planned and self._plan_token == self._engine.plan_token and key != self._plan_key and basis == "points" \
                 and self._plan_key is not None and len(self._plan_key[1]) == len(key[1]) and len(self._plan_key[2]) == len(key[2]):
@@ -257,7 +289,7 @@ class KroneckerStructure(torch.nn.Module):
                 self._engine.set_inducing(1, g2)
             self._plan_key = key
         elif not self._planned or self._plan_token != self._engine.plan_token or key != self._plan_key:
-            if self._scattered or self._masked:
+            if (self._scattered or self._masked) and not self._iter:
                 self._check_dense_workspace(basis, g1, g2)
             self._engine.plan(self.kind, basis, g1, self._x1, self.kind, basis, g2, self._x2, warm_start=self._warm,
                               b0_f32_kdelta=self._f32_mesh(), scattered=self._scattered)
@@ -274,7 +306,7 @@ class KroneckerStructure(torch.nn.Module):
         if M > 16384:
             raise ValueError(f"{type(self).__name__}: X is {'scattered' if self._scattered else 'a grid with holes'}, which takes the dense "
                              f"M-space solver, and M = m1 * m2 = {m1} * {m2} = {M} exceeds its limit of 16384 "
-                             f"(Engine.elbo_step_masked_iter handles larger M on masked grids)")
+                             f"(solver='auto' or 'iterative' handles larger M on grids with holes)")
         n_pair = N if self._scattered else max(len(self._x1), len(self._x2))
         need = 8.0 * (10.0 * M * M + 2.0 * (m1 * m1 + m2 * m2) * n_pair)
         free = torch.cuda.mem_get_info(self._engine.device)[0] if torch.cuda.is_available() else None
@@ -292,6 +324,9 @@ class KroneckerStructure(torch.nn.Module):
         self._plan()
         if self._scattered:
             return self._engine.elbo_step_scattered(self._Y, self._yy, theta)
+        if self._iter:
+            return self._engine.elbo_step_masked_iter(self._Y, self._W, self._nobs, self._yy, theta, n_probes=self.n_probes,
+                                                      tol=self.tol, max_iter=self.max_iter)
         if self._masked:
             return self._engine.elbo_step_masked(self._Y, self._W, self._nobs, self._yy, theta)
         return self._engine.elbo_step(self._Y, self._yy, theta)
@@ -310,6 +345,15 @@ class KroneckerStructure(torch.nn.Module):
         """gridded_kronecker_structure.py:1409-1433 == kronecker_structure.py:825-849.
         mean is flat (M,) with u = i1*m2 + i2 (callers do `.mean.reshape(m, m).T`)."""
         self._refresh()
+        if self._iter:
+            # iterative solver: the mean needs no solve and comes now; the variance of all M cells costs ceil(M / 64) block PCG
+            # solves and is computed on first use (q_v_at gives it for a few cells); there is no dense covariance
+            mean, _, _ = self._engine.qv_masked_iter(self._W, self._nobs, variance=False)
+
+            def var():
+                self._refresh()          # the engine may have been re-planned by another model since
+                return self._engine.qv_masked_iter(self._W, self._nobs, tol=self.tol, max_iter=self.max_iter)[1].cpu()
+            return MultivariateNormal(mean.reshape(-1).cpu(), var)
         if self._masked:
             mean, var = self._engine.qv_masked()
             return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
@@ -318,11 +362,26 @@ class KroneckerStructure(torch.nn.Module):
         return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
                                   cov_fn=lambda: self._engine.qv_cov().cpu())
 
+    def q_v_at(self, cells) -> MultivariateNormal:
+        """q(v) at a subset of the cells (flat indices u = i1*m2 + i2): mean and variance.  On the iterative solver this costs
+        ceil(len(cells) / 64) block solves instead of the ceil(M / 64) of q_v().variance; elsewhere it indexes q_v()."""
+        idx = torch.as_tensor(cells, dtype=torch.int64).reshape(-1)
+        self._plan()
+        if not self._iter:
+            qv = self.q_v()
+            return MultivariateNormal(qv.mean[idx], qv.variance[idx])
+        self._refresh()
+        mean, var, _ = self._engine.qv_masked_iter(self._W, self._nobs, cells=idx, tol=self.tol, max_iter=self.max_iter)
+        return MultivariateNormal(mean.reshape(-1).cpu()[idx], var.cpu())
+
     def posterior(self, x_star: torch.Tensor) -> MultivariateNormal:
         """kronecker_structure.py:199-230: mean and variance at x_star (N*, 2); `.covariance_matrix` (the reference's dense
         N* x N* matrix, :223-229) is materialised on first access (vggp_posterior_cov: N* <= 8192, M N* <= 2^27)."""
         self._refresh()
         xs = torch.as_tensor(x_star, dtype=torch.float64)
+        if self._iter:                   # (no dense covariance on the iterative solver: .covariance_matrix raises)
+            mean, var, _ = self._engine.posterior_masked_iter(xs, self._W, self._nobs, tol=self.tol, max_iter=self.max_iter)
+            return MultivariateNormal(mean.cpu(), var.cpu())
         post = self._engine.posterior_masked if self._masked else self._engine.posterior
         mean, var = post(xs)
 
@@ -495,6 +554,12 @@ class Matern12VFFGP(KroneckerStructure):
         return "vff", g1, g2
 
 
+def _no_gridded_readout(model):
+    if model._iter:
+        raise NotImplementedError(f"{type(model).__name__}: the gridded read-out q_v() is not available on the iterative masked solver "
+                                  f"(q_u(), q_v_at() on the inducing features and posterior() are)")
+
+
 def _b0_kvv_diag_unit(delta: float, ell: float) -> float:
     """diag of the unit-outputscale B0 Gram matrix (gridded_kronecker_structure.py:341-394): ell^2 * 2 (e^{-d/l} + d/l - 1)."""
     r = delta / ell
@@ -533,6 +598,7 @@ class GriddedMatern12VFFGP(Matern12VFFGP):
     def q_v(self, psd: bool = True, literal: bool = True) -> MultivariateNormal:
         """:634-654 (mean and the diagonal of the covariance; flat index a * nsplines + b)."""
         self._refresh()
+        _no_gridded_readout(self)
         C1 = self._Kvu_along_dim(self.mesh_1, self.dim1lims[0], self.omegas_1)
         C2 = self._Kvu_along_dim(self.mesh_2, self.dim2lims[0], self.omegas_2)
         l1 = self.kernel_1.base_kernel.lengthscale.reshape(()).item()
@@ -578,6 +644,7 @@ class _GriddedReadout:
         """mean and the diagonal of the covariance of the B0 cell features (flat index a * nsplines + b); the variance is the
         reference's own expression (literal=True) unless literal=False asks for the conditional variance under q(u)."""
         self._refresh()
+        _no_gridded_readout(self)
         l1 = self.kernel_1.base_kernel.lengthscale.reshape(()).item()
         l2 = self.kernel_2.base_kernel.lengthscale.reshape(()).item()
         kd1 = torch.full((self.nsplines,), _b0_kvv_diag_unit(float(self.b0_delta_1.double()), l1), dtype=torch.float64)
@@ -798,6 +865,7 @@ class GriddedMatern12SVGP(_GriddedReadout, KroneckerStructure):
             self._z1, self._z2, self._u_of_row = _detect_cartesian(Zt)
         else:
             self.Z = torch.nn.Parameter(Zt.clone(), requires_grad=bool(train_z))
+            self._no_iterative("paired inducing points (inducing='general')")
             if self._masked:                                    # a grid with holes is its observed points
                 self._as_scattered()
             self._masked = True                                 # read-outs: the dense M-space ones (vggp_*_masked)
