@@ -225,6 +225,40 @@ int vggp_qv_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, const int6
 int vggp_posterior_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, const double* xs1, const double* xs2,
                                int64_t n_star, double tol, int max_iter, int block, double* mean, double* var, vggp_info* info,
                                void* stream);
+/* The scattered step WITHOUT the M x M matrices and without any m_d^2 x N or m_d x columns x N buffer -- along-track data beyond
+ * the dense solver of vggp_elbo_step_scattered (M = m1 m2 > 16384, or m_d^2 N >= 2^31) or where its O(M^2 N + M^3) is too slow.
+ * The iterative masked step with the sum over observed grid nodes replaced by a sum over the points (a Khatri-Rao operator),
+ *     Sigma~ V = V + rho sum_k b1_k (b1_k^T V b2_k) b2_k^T,     B_d = L0_d^-1 A0_d(x_d)  (m_d x N, one column per point),
+ * applied by two fused fp64-MFMA kernels (vggp_kr_field, vggp_kr_back below); preconditioner P = I + (rho / N) G1 (x) G2 with
+ * G_d = B_d B_d^T, diagonal in the Kronecker eigenbasis (the independence approximation E[Phi] = G1 (x) G2 / N: exact when the
+ * points form a full grid); PCG, Lanczos quadrature on FIXED probes and control-variate traces as vggp_elbo_step_masked_iter.
+ * Bitwise reproducible (no floating-point atomics).  Workspace O(M cols + (m1 + m2) N + cols N), cols = n_probes + 1.
+ *   y DEVICE [N], yy = sum y^2, theta as vggp_elbo_step_scattered; n_probes <= 0: 16 (at most 63); tol <= 0: 1e-10; max_iter <= 0: 100
+ *   info->rounds1 = PCG iterations, info->sweeps1 = probes.  Any m_d <= 256.
+ * Accuracy: a0 = Sigma~^-1 c0, and with it both mean read-outs below, is exact to the PCG tolerance wherever the PCG converges.
+ * The stochastic ELBO and gradient match the iterative masked step's quality (ELBO 1e-5 relative, gradient 1e-4 of its largest
+ * component against vggp_elbo_step_scattered, 16 probes) when the points outnumber the inducing features by about 60 or more;
+ * they degrade to 1e-3 .. 1e-2 when N is about M, where few tracks also cost PCG iterations.  No tolerance is stated there.
+ * Needs a context planned with VGGP_FLAG_SCATTERED (VGGP_EINVAL otherwise, and on paired or multi-rank contexts); VGGP_ENOCONV when
+ * the PCG does not converge.  The kept-basis rules are the masked iterative step's (VGGP_ITER_COLD_BASIS honoured).  The dense
+ * read-outs (vggp_qv_masked, ...) and vggp_zgrad_scattered return VGGP_ESTATE after this step. */
+int vggp_elbo_step_scattered_iter(vggp_ctx* ctx, const double* y, double yy, const double theta[5], int n_probes, double tol,
+                                  int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream);
+/* Mean read-outs of the iterative scattered step; both need only a0: mean = (s1 s2 / sigma^2) t^T a0.  VGGP_ESTATE unless the LAST
+ * finished step on the context was a successful vggp_elbo_step_scattered_iter.  VARIANCES ARE NOT PROVIDED YET: they are one block
+ * PCG solve with the same operator (as vggp_qv_masked_iter does for grids) and are the follow-up to these entries.
+ *   vggp_qv_scattered_iter         mean DEVICE [m1][m2] = L0_1 A0 L0_2^T scaled as vggp_qv_masked_iter scales it (e_d = -1 for VFF / B1)
+ *   vggp_posterior_scattered_iter  xs1, xs2 DEVICE [n_star]; mean DEVICE [n_star] */
+int vggp_qv_scattered_iter(vggp_ctx* ctx, double* mean, void* stream);
+int vggp_posterior_scattered_iter(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t n_star, double* mean, void* stream);
+/* Building blocks of that step, exported for tests: the two kernels on caller-supplied DEVICE arrays.  L [m1][N], R [m2][N] (one
+ * column per point), block vectors [m1][nb][m2], fields [nb][N]; 1 <= m_d <= 256, 1 <= nb <= 64.  The context need not be planned.
+ *   field  F[c][k]      = sum_a L[a][k] sum_b V[a][c][b] R[b][k]
+ *   back   out[a][c][b] = sum_k L[a][k] F[c][k] R[b][k]      (reduction split over workgroups, slabs summed in fixed order) */
+int vggp_kr_field(vggp_ctx* ctx, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                  double* F, void* stream);
+int vggp_kr_back(vggp_ctx* ctx, const double* L, const double* R, const double* F, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                 double* out, void* stream);
 /* q(v) of the last masked step: mean and covariance diagonal, DEVICE [m1][m2]. */
 int vggp_qv_masked(vggp_ctx* ctx, double* mean, double* var, void* stream);
 /* posterior(x*) of the last masked step (kronecker_structure.py:199-230); arguments as vggp_posterior. */

@@ -63,6 +63,11 @@ SYMBOLS = {
     "vggp_qv_masked_iter": (_I, [_P, _P, _D, C.POINTER(_I64), _I64, _D, _I, _I, _P, _P, C.POINTER(Info), _P]),
     "vggp_posterior_masked_iter": (_I, [_P, _P, _D, _P, _P, _I64, _D, _I, _I, _P, _P, C.POINTER(Info), _P]),
     "vggp_elbo_step_scattered": (_I, [_P, _P, _D, C.POINTER(_D), C.POINTER(_D), C.POINTER(_D), C.POINTER(Info), _P]),
+    "vggp_elbo_step_scattered_iter": (_I, [_P, _P, _D, C.POINTER(_D), _I, _D, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(Info), _P]),
+    "vggp_qv_scattered_iter": (_I, [_P, _P, _P]),
+    "vggp_posterior_scattered_iter": (_I, [_P, _P, _P, _I64, _P, _P]),
+    "vggp_kr_field": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "vggp_kr_back": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "vggp_qv_masked": (_I, [_P, _P, _P, _P]),
     "vggp_qv": (_I, [_P, _P, _P, _P]),
     "vggp_qv_cov": (_I, [_P, _P, _P]),

@@ -62,7 +62,8 @@ struct vggp_ctx {
     int gh_slabs[2] = {1, 1}, cc_slabs = 1;      // split-K slab counts actually produced by the last partials launch
     long payload_len = 0;
     bool have_partials = false, have_step = false, have_masked = false;
-    bool have_iter = false;          // the last finished step was a successful vggp_elbo_step_masked_iter (its read-outs: masked.hip)
+    bool have_iter = false;          // the last finished step was a successful vggp_elbo_step_masked_iter / vggp_elbo_step_scattered_iter
+                                     // (which of the two: the plan's VGGP_FLAG_SCATTERED; their read-outs: masked.hip)
     void* masked = nullptr;          // VgMasked workspace (masked.hip), allocated on first use
     void* paired = nullptr;          // VgPaired workspace (paired.hip): allocated by a plan with VGGP_FLAG_PAIRED_Z
     bool is_paired = false;          // the current plan is a paired one: only the entries listed in vggp.h apply
@@ -169,6 +170,11 @@ int vg_paired_posterior_cov(vggp_ctx* c, const double* xs1, const double* xs2, i
         }                                                                                                               \
     } while (0)
 void vg_masked_new_plan(vggp_ctx* c);
+// the Khatri-Rao operator of the iterative scattered step (kr.hip): L [m1][N], R [m2][N], block vectors [m1][nb][m2], fields [nb][N]
+hipError_t vg_kr_field_launch(const double* L, const double* R, const double* V, int m1, int m2, long N, int nb, double* F, hipStream_t st);
+size_t vg_kr_back_scratch(int m1, int m2, long N, int nb);      // doubles of split scratch vg_kr_back_launch needs (bounded whatever N)
+hipError_t vg_kr_back_launch(const double* L, const double* R, const double* F, int m1, int m2, long N, int nb, double* out, double* scratch,
+                             hipStream_t st);
 // batch of triangular solves, each in place on its X (api.hip trsm_batch: element (row k, column c) at X[k * sk + c * sc])
 #define VG_TRSM_BLK 128
 struct VgTrsmSpec {

@@ -573,6 +573,7 @@ extern "C" int vggp_elbo_step_scattered(vggp_ctx* c, const double* y, double yy,
     VG_REQUIRE(y && theta && elbo_out && grad_out, "vggp_elbo_step_scattered: null argument");
     VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "vggp_elbo_step_scattered: plan the context with VGGP_FLAG_SCATTERED");
     c->have_masked = false;
+    c->have_iter = false;            // (the read-outs of vggp_elbo_step_scattered_iter belong to that step alone)
     const long m1 = c->desc.m1, m2 = c->desc.m2, N = c->desc.n1, M = m1 * m2;
     VG_REQUIRE(M <= VGM_MAX_M, "vggp_elbo_step_scattered: M = m1*m2 = %ld too large for the dense solver (<= %d)", M, VGM_MAX_M);
     VG_REQUIRE(m1 * m1 * N < (1L << 31) && m2 * m2 * N < (1L << 31) && M * M < (1L << 31) * 4, "scattered problem too large");
@@ -1872,4 +1873,443 @@ extern "C" int vggp_qv_masked_iter(vggp_ctx* c, const double* W, double n_obs, c
 extern "C" int vggp_posterior_masked_iter(vggp_ctx* c, const double* W, double n_obs, const double* xs1, const double* xs2, int64_t ns,
                                           double tol, int max_iter, int block, double* mean, double* var, vggp_info* info, void* stream) {
     return vgi_readout_run(c, "vggp_posterior_masked_iter", 0, W, n_obs, nullptr, xs1, xs2, ns, tol, max_iter, block, mean, var, info, stream);
+}
+
+// ================================================================================================================================
+// Iterative SCATTERED step (vggp_elbo_step_scattered_iter): the iterative masked step above with the sum over the observed grid nodes
+// replaced by a sum over the points -- a Khatri-Rao operator instead of a masked Kronecker one,
+//     Sigma~ V = V + rho sum_k b1_k (b1_k^T V b2_k) b2_k^T,
+// applied by the two kernels of kr.hip (field: the per-point scalars; back: their weighted outer products), so that neither an
+// M x M matrix nor an m_d x nbc x N / m_d^2 x N buffer exists.  Preconditioner P = I + (rho / N) G1 (x) G2, G_d = B_d B_d^T over the
+// points (the independence approximation E[Phi] = G1 (x) G2 / N; exact for a full grid): the masked step's with p = 1 / N, the same
+// kept-basis rules, probes, PCG, Lanczos quadrature and control-variate traces.  Every masked field W^T o (L^T V R) becomes the
+// per-point vector l_k^T V r_k ([nbc][N]).  Specification: tests/scattered_iter_spec.py; scalar terms as elbo_step_scattered.
+// ================================================================================================================================
+// part[block] = sum over this block's share of a[i] b[i] (fixed order); summed by vgi_sum_kernel
+__global__ __launch_bounds__(256) void vgs_dot_part_kernel(const double* a, const double* b, long n, double* part) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += a[i] * b[i];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ void vgs_scale_mean_kernel(double* x, long n, const double* theta) {       // x *= s1 s2 / sigma^2
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] *= theta[2] * theta[3] / theta[4];
+}
+
+struct VgSIter {
+    VgIter it;            // block vectors, PCG state, rotated factors (Rr*, Rv*, RR*, RRV*: [m_d][N]); F0..F2: [nbc][N]; Wt, T1, TW, TWv unused
+    double* krs;          // split scratch of the back kernel
+    double* fpart;        // [1024] partial sums of the field dot products
+};
+
+static int vgs_prepare(VgMasked& w, VgSIter& s, int nbc, int maxit) {
+    const size_t m1 = w.m1, m2 = w.m2, N = w.n1, M = w.M, mx = std::max(m1, m2);
+    VgIter& it = s.it;
+    size_t off = 0;
+    char* base = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        off = 0;
+        auto take = [&](size_t count) {
+            off = (off + 255) & ~size_t(255);
+            double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
+            off += count * sizeof(double);
+            return p;
+        };
+        it.Wt = nullptr; it.T1 = nullptr; it.TW = nullptr; it.TWv = nullptr;
+        it.X = take(M * nbc); it.R = take(M * nbc); it.Zp = take(M * nbc); it.Pd = take(M * nbc); it.AP = take(M * nbc);
+        it.Wz = take(M * nbc); it.Tm = take(M * nbc); it.Tm2 = take(M * nbc);
+        it.F0 = take(N * nbc); it.F1 = take(N * nbc); it.F2 = take(N * nbc);
+        it.alh = take((size_t)maxit * nbc); it.beh = take((size_t)maxit * nbc);
+        it.col = take(8 * (size_t)nbc);
+        it.Rr1 = take(m1 * N); it.Rv1 = take(m1 * N); it.RR1 = take(m1 * N); it.RRV1 = take(m1 * N);
+        it.Rr2 = take(m2 * N); it.Rv2 = take(m2 * N); it.RR2 = take(m2 * N); it.RRV2 = take(m2 * N);
+        it.Ex = take(M);
+        it.dg1 = take(m1); it.dg2 = take(m2); it.Tq = take(mx * mx);
+        it.Qk1 = take(m1 * m1); it.Qk2 = take(m2 * m2);
+        it.ts = take(64 + (size_t)nbc);
+        s.fpart = take(1024);
+        s.krs = take(vg_kr_back_scratch((int)m1, (int)m2, (long)N, nbc));
+        it.nact = reinterpret_cast<int*>(take(8));
+        if (pass == 0) {
+            const size_t need = off + 4096;
+            if (w.ibytes < need || w.ib_nbc != nbc || w.ib_maxit != maxit) w.ib_valid = false;      // (the layout moves: the kept basis is gone)
+            w.ib_nbc = nbc; w.ib_maxit = maxit;
+            if (w.ibytes < need) {
+                if (w.imem) { VG_HIP(hipFree(w.imem)); w.imem = nullptr; w.ibytes = 0; }
+                size_t free_b = 0, total_b = 0;
+                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
+                    vg_set_error("the workspace of the iterative scattered step needs %.1f GiB (m1 = %d, m2 = %d, N = %ld, %d columns) but only "
+                                 "%.1f GiB of device memory are free", (double)need / 1073741824.0, w.m1, w.m2, (long)N, nbc,
+                                 (double)free_b / 1073741824.0);
+                    return VGGP_ENOMEM;
+                }
+                VG_HIP(hipMalloc(&w.imem, need));
+                w.ibytes = need;
+            }
+            base = reinterpret_cast<char*>(w.imem);
+        }
+    }
+    it.nbc = nbc; it.maxit = maxit;
+    return VGGP_OK;
+}
+
+// entry checks shared by the step and its read-outs
+static int vgs_check(vggp_ctx* c, const char* fn) {
+    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
+    VG_NOT_PAIRED(c, fn);
+    VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: plan the context with VGGP_FLAG_SCATTERED", fn);
+    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
+    return VGGP_OK;
+}
+
+static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const double theta[5], int n_probes, double tol, int max_iter,
+                               double* elbo_out, double grad_out[5], vggp_info* info, void* stream) {
+    static const char* fn = "vggp_elbo_step_scattered_iter";
+    int rc = vgs_check(c, fn);
+    if (rc) return rc;
+    VG_REQUIRE(y && theta && elbo_out && grad_out, "%s: null argument", fn);
+    c->have_masked = false;
+    c->have_iter = false;
+    if (n_probes <= 0) n_probes = 16;
+    if (max_iter <= 0) max_iter = 100;
+    if (!(tol > 0.0)) tol = 1e-10;
+    VG_REQUIRE(n_probes <= 63 && max_iter <= VGI_MAXIT, "%s: n_probes <= 63, max_iter <= %d", fn, VGI_MAXIT);
+    const long m1 = c->desc.m1, m2 = c->desc.m2, N = c->desc.n1, M = m1 * m2;
+    const int nbc = n_probes + 1;
+    VG_REQUIRE(N * nbc < (1L << 31) && M * nbc < (1L << 31), "%s: problem too large", fn);
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    for (int i = 0; i < 5; ++i) {
+        VG_REQUIRE(theta[i] > 0.0 && std::isfinite(theta[i]), "theta[%d]=%g must be positive and finite", i, theta[i]);
+        c->h_theta[i] = theta[i];
+    }
+    if ((rc = vgm_prepare(c, /*iter=*/true))) return rc;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgSIter s;
+    if ((rc = vgs_prepare(w, s, nbc, max_iter))) return rc;
+    VgIter& it = s.it;
+    if ((rc = vg_partials_enqueue(c, nullptr, nullptr, st))) return rc;          // factors at the points: B|V, Mk (unit outputscale)
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const double *B1 = d1.BV, *V1 = d1.BV + m1 * N, *B2 = d2.BV, *V2 = d2.BV + m2 * N;
+    double *C0 = w.mpay + 2 * m2 * m2, *C1 = C0 + M, *C2 = C1 + M;
+    // projections C0 = B1 diag(y) B2^T, C1 = V1 diag(y) B2^T, C2 = B1 diag(y) V2^T and the per-point statistics: the dense step's
+    VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * N, st, B1, y, (int)m1, N, w.B1s);
+    VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * N, st, V1, y, (int)m1, N, w.UV);           // (UV is free until the a0 stage)
+    if ((rc = gemm_longk(w.B1s, N, 1, B2, 1, N, C0, (int)m1, (int)m2, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(w.UV, N, 1, B2, 1, N, C1, (int)m1, (int)m2, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(w.B1s, N, 1, V2, 1, N, C2, (int)m1, (int)m2, (int)N, w.T, st))) return rc;
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B1, B1, (int)m1, N, w.nb1);
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B2, B2, (int)m2, N, w.nb2);
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, V1, B1, (int)m1, N, w.hv1);
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, V2, B2, (int)m2, N, w.hv2);
+    // Gram matrices over the points
+    if ((rc = gemm_longk(B1, N, 1, B1, 1, N, d1.GH, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(B2, N, 1, B2, 1, N, d2.GH, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
+    bool reused = false;
+    {   // eigenbasis of the preconditioner: the kept-basis rules of the masked iterative step (see there)
+        static const bool always = getenv("VGGP_ITER_COLD_BASIS") != nullptr;
+        const double* G[2] = {d1.GH, d2.GH};
+        const bool reuse = !always && w.ib_valid && w.ib_age < 64 && w.ib_last_its <= w.ib_ref_its + 4 && d1.kind != VGGP_KIND_RBF &&
+                           d2.kind != VGGP_KIND_RBF;
+        reused = reuse;
+        if (reuse) {
+            double* Qk[2] = {it.Qk1, it.Qk2};
+            for (int k = 0; k < 2; ++k) {
+                VgDim& d = c->d[k];
+                VG_HIP(hipMemcpyAsync(d.Qt, Qk[k], sizeof(double) * d.m * d.m, hipMemcpyDeviceToDevice, st));
+                if ((rc = gemm1(d.Qt, d.m, 1, G[k], d.m, 1, it.Tq, d.m, d.m, d.m, d.m, st))) return rc;
+                VGM_LAUNCH1D(vgi_rowdot_kernel, d.m, st, it.Tq, d.Qt, d.m, d.lam0);
+            }
+            ++w.ib_age;
+            w.ib_fresh = false;
+        } else {
+            VgEigJob ej[2];
+            for (int k = 0; k < 2; ++k) {
+                VgDim& d = c->d[k];
+                ej[k] = VgEigJob{G[k], d.lam0, d.Qt, nullptr, d.gwork, d.rotlog, d.roundlog, d.counters, d.m, d.max_rounds,
+                                 (long)vg_eigh_log_bytes(d.m), 0};
+                ej[k].perm = d.perm;
+                ej[k].err = d.status + 1;
+            }
+            VG_HIP(vg_eigh_launch(ej, 2, st));
+            VG_HIP(hipMemcpyAsync(it.Qk1, d1.Qt, sizeof(double) * m1 * m1, hipMemcpyDeviceToDevice, st));
+            VG_HIP(hipMemcpyAsync(it.Qk2, d2.Qt, sizeof(double) * m2 * m2, hipMemcpyDeviceToDevice, st));
+            w.ib_valid = false;
+            w.ib_fresh = true;
+        }
+    }
+    const double p = 1.0 / (double)N;
+    const long nb = M * nbc, nf = N * nbc;
+    auto field = [&](const double* L, const double* V, const double* R, double* F) -> int {
+        VG_HIP(vg_kr_field_launch(L, R, V, (int)m1, (int)m2, N, nbc, F, st));
+        return VGGP_OK;
+    };
+    VGM_LAUNCH1D(vgi_probe_kernel, nb, st, it.X, (int)m1, nbc, (int)m2, 0x5647475000000001ULL);
+    if ((rc = vgi_rot(c, w, it, it.X, it.R, 1, 1, p, st))) return rc;
+    if ((rc = vgi_rot(c, w, it, it.X, it.Wz, 2, 1, p, st))) return rc;
+    VGM_LAUNCH1D(vgi_col_kernel, M, st, it.R, C0, (int)m1, nbc, (int)m2, 0, 0);
+    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
+    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
+    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col, it.col + 3 * nbc);
+    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
+    int iters = 0, nact = nbc;
+    for (int k = 0; k < max_iter && nact > 0; ++k) {
+        // AP = Pd + rho sum_k b1_k (b1_k^T Pd b2_k) b2_k^T
+        if ((rc = field(B1, it.Pd, B2, it.F0))) return rc;
+        VG_HIP(vg_kr_back_launch(B1, B2, it.F0, (int)m1, (int)m2, N, nbc, it.AP, s.krs, st));
+        VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
+        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
+                           (int)m2, it.col + nbc, (double*)nullptr);
+        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, k, tol, it.alh, it.beh, it.nact);
+        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 1);
+        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
+        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col + 5 * nbc,
+                           it.col + 3 * nbc);
+        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, k, tol, it.alh, it.beh, it.nact);
+        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 2);
+        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipStreamSynchronize(st));
+        nact = c->h_out->counters[0][0];
+        iters = k + 1;
+        if (reused && nact > 0 && iters > w.ib_ref_its + 12) {      // the kept basis has drifted too far: not worth iterating on
+            w.ib_valid = false;
+            return VGI_ESTALE;
+        }
+    }
+    if (nact > 0) { vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left)", fn, tol, max_iter, nact); return VGGP_ENOCONV; }
+    // log det: log|P| + the quadratures
+    VG_HIP(hipMemsetAsync(it.ts, 0, 64 * sizeof(double), st));
+    VG_HIP(hipMemsetAsync(w.cholstatus, 0, sizeof(int), st));
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr,
+                       (const double*)nullptr, (const double*)nullptr, 1, it.ts + 0);
+    hipLaunchKernelGGL(vgi_slq_kernel, dim3(1), dim3(64), 0, st, it.alh, it.beh, it.col, nbc, (double)M, it.ts + 32, w.cholstatus);
+    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.ts + 32, n_probes, it.ts + 1, 0);
+    // a0 and the a0 terms of the gradient (the dense scattered step's)
+    VGM_LAUNCH1D(vgi_col_kernel, M, st, it.X, w.a0, (int)m1, nbc, (int)m2, 0, 1);
+    if ((rc = gemm1(d1.Mk, m1, 1, w.a0, m2, 1, w.MkA1, (int)m2, (int)m1, (int)m2, (int)m1, st))) return rc;
+    if ((rc = gemm1(w.a0, m2, 1, d2.Mk, m2, 1, w.MkA2, (int)m2, (int)m1, (int)m2, (int)m2, st))) return rc;
+    if ((rc = gemm1(w.a0, m2, 1, B2, N, 1, w.UB, (int)N, (int)m1, (int)N, (int)m2, st))) return rc;
+    if ((rc = gemm1(w.a0, m2, 1, V2, N, 1, w.UV, (int)N, (int)m1, (int)N, (int)m2, st))) return rc;
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B1, w.UB, (int)m1, N, w.Zb);
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, V1, w.UB, (int)m1, N, w.Zv1);
+    VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B1, w.UV, (int)m1, N, w.Zv2);
+    VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * N, st, B1, w.nb2, (int)m1, N, w.B1s);
+    VGM_LAUNCH1D(vgm_scalecols_kernel, m2 * N, st, B2, w.nb1, (int)m2, N, w.B2s);
+    if ((rc = gemm_longk(w.B1s, N, 1, B1, 1, N, w.PT1, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(w.B2s, N, 1, B2, 1, N, w.PT2, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
+    // dU = Sigma~^-1 z - P^-1 z (probe columns); stochastic parts of the traces: per-point fields of dU and of Wz
+    VGM_LAUNCH1D(vgi_sub_kernel, nb, st, it.X, it.Wz, nb, it.Zp);
+    double* dU = it.Zp;
+    auto fsum = [&](const double* Fa, const double* Fb, double* out) {          // sum over the probe columns c >= 1 and the points
+        hipLaunchKernelGGL(vgs_dot_part_kernel, dim3(1024), dim3(256), 0, st, Fa + N, Fb + N, nf - N, s.fpart);
+        hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, s.fpart, 1024, out, 0);
+    };
+    if ((rc = field(B1, it.Wz, B2, it.F0))) return rc;              // F0 = Fw^BB
+    if ((rc = field(B1, dU, B2, it.F1))) return rc;                 // F1 = Fu^BB
+    fsum(it.F1, it.F0, it.ts + 3);
+    if ((rc = field(V1, dU, B2, it.F2))) return rc;                 // Fu^VB
+    fsum(it.F2, it.F0, it.ts + 6);
+    if ((rc = field(B1, dU, V2, it.F2))) return rc;                 // Fu^BV
+    fsum(it.F2, it.F0, it.ts + 9);
+    if ((rc = field(V1, it.Wz, B2, it.F0))) return rc;              // Fw^VB
+    fsum(it.F1, it.F0, it.ts + 5);
+    if ((rc = field(B1, it.Wz, V2, it.F0))) return rc;              // Fw^BV
+    fsum(it.F1, it.F0, it.ts + 8);
+    // Mk terms: <dU, Mk1 Wz>, <dU, Wz Mk2^T>
+    double* cs = it.ts + 64;                                        // [nbc] per-column sums
+    if ((rc = gemm1(d1.Mk, m1, 1, it.Wz, (long)nbc * m2, 1, it.Tm, nbc * (int)m2, (int)m1, nbc * (int)m2, (int)m1, st))) return rc;
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
+                       (int)m2, cs, (double*)nullptr);
+    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, cs, nbc, it.ts + 11, 1);
+    if ((rc = gemm1(it.Wz, m2, 1, d2.Mk, 1, m2, it.Tm, (int)m2, (int)(m1 * nbc), (int)m2, (int)m2, st))) return rc;
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
+                       (int)m2, cs, (double*)nullptr);
+    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, cs, nbc, it.ts + 13, 1);
+    // exact parts tr(P^-1 Phi(.)) = sum (1/dP) o ((Ra o Rb)(Sa o Sb)^T): factors rotated into the eigenbasis of P, one m1 x m2 GEMM
+    // over the points each
+    if ((rc = gemm1(d1.Qt, m1, 1, B1, N, 1, it.Rr1, (int)N, (int)m1, (int)N, (int)m1, st))) return rc;
+    if ((rc = gemm1(d1.Qt, m1, 1, V1, N, 1, it.Rv1, (int)N, (int)m1, (int)N, (int)m1, st))) return rc;
+    if ((rc = gemm1(d2.Qt, m2, 1, B2, N, 1, it.Rr2, (int)N, (int)m2, (int)N, (int)m2, st))) return rc;
+    if ((rc = gemm1(d2.Qt, m2, 1, V2, N, 1, it.Rv2, (int)N, (int)m2, (int)N, (int)m2, st))) return rc;
+    VGM_LAUNCH1D(vgi_mul_kernel, m1 * N, st, it.Rr1, it.Rr1, m1 * N, it.RR1);
+    VGM_LAUNCH1D(vgi_mul_kernel, m1 * N, st, it.Rr1, it.Rv1, m1 * N, it.RRV1);
+    VGM_LAUNCH1D(vgi_mul_kernel, m2 * N, st, it.Rr2, it.Rr2, m2 * N, it.RR2);
+    VGM_LAUNCH1D(vgi_mul_kernel, m2 * N, st, it.Rr2, it.Rv2, m2 * N, it.RRV2);
+    auto exact = [&](const double* RRa, const double* RRb, double* out) -> int {
+        int r2 = gemm_longk(RRa, N, 1, RRb, 1, N, it.Ex, (int)m1, (int)m2, (int)N, w.T, st);
+        if (r2) return r2;
+        hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, it.Ex,
+                           (const double*)nullptr, (const double*)nullptr, 0, out);
+        return VGGP_OK;
+    };
+    if ((rc = exact(it.RR1, it.RR2, it.ts + 2))) return rc;
+    if ((rc = exact(it.RRV1, it.RR2, it.ts + 4))) return rc;
+    if ((rc = exact(it.RR1, it.RRV2, it.ts + 7))) return rc;
+    if ((rc = gemm1(d1.Qt, m1, 1, d1.Mk, m1, 1, it.Tq, (int)m1, (int)m1, (int)m1, (int)m1, st))) return rc;
+    VGM_LAUNCH1D(vgi_rowdot_kernel, m1, st, it.Tq, d1.Qt, (int)m1, it.dg1);
+    if ((rc = gemm1(d2.Qt, m2, 1, d2.Mk, m2, 1, it.Tq, (int)m2, (int)m2, (int)m2, (int)m2, st))) return rc;
+    VGM_LAUNCH1D(vgi_rowdot_kernel, m2, st, it.Tq, d2.Qt, (int)m2, it.dg2);
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr, it.dg1,
+                       (const double*)nullptr, 0, it.ts + 10);
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr,
+                       (const double*)nullptr, it.dg2, 0, it.ts + 12);
+    // the dense scattered step's reductions that do not involve Sigma~^-1 as a matrix; the six that do come from the combine kernel
+    VgmRedArgs ra;
+    ra.njobs = RJ_COUNT;
+    ra.partial = w.partial;
+    auto job = [&](int k, const double* a, const double* b, long n, long sa, long sb, int op) {
+        ra.job[k] = VgmRedJob{a, b, nullptr, n, sa, sb, op};
+    };
+    for (int k = 0; k < RJ_COUNT; ++k) job(k, w.a0, w.a0, 0, 1, 1, 0);
+    job(RJ_Q, C0, w.a0, M, 1, 1, 0);
+    job(RJ_AA, w.a0, w.a0, M, 1, 1, 0);
+    job(RJ_TRPHI, w.nb1, w.nb2, N, 1, 1, 0);
+    job(RJ_TRMK1, d1.Mk, nullptr, m1, m1 + 1, 0, 2);
+    job(RJ_AC1, w.a0, C1, M, 1, 1, 0);
+    job(RJ_MKA1, w.MkA1, w.a0, M, 1, 1, 0);
+    job(RJ_Z1, w.Zb, w.Zv1, N, 1, 1, 0);
+    job(RJ_HV1, w.hv1, w.nb2, N, 1, 1, 0);
+    job(RJ_MK1PT, d1.Mk, w.PT1, m1 * m1, 1, 1, 0);
+    job(RJ_TRMK2, d2.Mk, nullptr, m2, m2 + 1, 0, 2);
+    job(RJ_AC2, w.a0, C2, M, 1, 1, 0);
+    job(RJ_MKA2, w.MkA2, w.a0, M, 1, 1, 0);
+    job(RJ_Z2, w.Zb, w.Zv2, N, 1, 1, 0);
+    job(RJ_HV2, w.hv2, w.nb1, N, 1, 1, 0);
+    job(RJ_MK2PT, d2.Mk, w.PT2, m2 * m2, 1, 1, 0);
+    hipLaunchKernelGGL(vgm_red_kernel, dim3(VG_MD_NPART, RJ_COUNT), dim3(256), 0, st, ra);
+    hipLaunchKernelGGL(vgm_sum_kernel, dim3(1), dim3(64), 0, st, w.partial, w.scal, 0u, 1);
+    hipLaunchKernelGGL(vgi_combine_kernel, dim3(1), dim3(64), 0, st, it.ts, c->theta, (double)M, n_probes, w.scal);
+    VgmFinalArgs fa{c->theta, w.scal, w.out, (double)N, yy, (int)m1, (int)m2};
+    hipLaunchKernelGGL(vgm_final_kernel, dim3(1), dim3(64), 0, st, fa);
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipMemcpyAsync(c->h_out->out, w.out, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
+    for (int k = 0; k < 2; ++k) {
+        VG_HIP(hipMemcpyAsync(&c->h_out->jitter[k], c->d[k].jitter, sizeof(double), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipMemcpyAsync(&c->h_out->status[k], c->d[k].status, sizeof(int), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipMemcpyAsync(&c->h_out->counters[k][2], c->d[k].counters + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    VG_HIP(hipMemcpyAsync(&c->h_out->counters[1][3], w.cholstatus, sizeof(int), hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));
+    *elbo_out = c->h_out->out[0];
+    for (int i = 0; i < 5; ++i) grad_out[i] = c->h_out->out[1 + i];
+    int status = c->h_out->status[0] ? c->h_out->status[0] : (c->h_out->status[1] ? c->h_out->status[1] : 0);
+    if (!status) status = c->h_out->counters[0][2] ? c->h_out->counters[0][2] : c->h_out->counters[1][2];
+    if (info) {
+        info->jitter1 = c->h_out->jitter[0]; info->jitter2 = c->h_out->jitter[1];
+        info->sweeps1 = n_probes; info->sweeps2 = 0; info->rounds1 = iters; info->rounds2 = 0;
+        info->status = status; info->polished = 0;
+    }
+    if (status == VGGP_ENOTPD) { vg_set_error("iterative scattered step: a factor is not positive definite"); return VGGP_ENOTPD; }
+    if (status) { vg_set_error("iterative scattered step: the preconditioner's eigensolver failed (status %d)", status); return VGGP_ENOCONV; }
+    if (c->h_out->counters[1][3]) { vg_set_error("iterative scattered step: the Lanczos quadrature failed (code %d)", c->h_out->counters[1][3]); return VGGP_ENOCONV; }
+    if (w.ib_fresh) { w.ib_valid = true; w.ib_age = 0; w.ib_ref_its = iters; }
+    w.ib_last_its = iters;
+    c->have_step = false; c->have_partials = false;
+    c->have_iter = true;             // a0 and the factors are there for vggp_qv_scattered_iter / vggp_posterior_scattered_iter
+    return VGGP_OK;
+}
+
+extern "C" int vggp_elbo_step_scattered_iter(vggp_ctx* c, const double* y, double yy, const double theta[5], int n_probes, double tol,
+                                             int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream) {
+    int rc = scattered_iter_once(c, y, yy, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
+    if (rc == VGI_ESTALE) rc = scattered_iter_once(c, y, yy, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
+    if (rc == VGI_ESTALE) { vg_set_error("vggp_elbo_step_scattered_iter: internal (stale basis after a cold solve)"); rc = VGGP_ESTATE; }
+    return rc;
+}
+
+// q(v) mean of the last iterative scattered step: (s1 s2 / v) L1 A0 L2^T, scaled as vggp_qv_masked_iter scales it (no solve)
+extern "C" int vggp_qv_scattered_iter(vggp_ctx* c, double* mean, void* stream) {
+    static const char* fn = "vggp_qv_scattered_iter";
+    int rc = vgs_check(c, fn);
+    if (rc) return rc;
+    VG_REQUIRE(mean, "%s: null output", fn);
+    if (!c->have_iter || !c->masked) { vg_set_error("%s: no finished vggp_elbo_step_scattered_iter on this context", fn); return VGGP_ESTATE; }
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const long m1 = w.m1, m2 = w.m2, M = w.M;
+    const int e1 = (d1.basis == VGGP_BASIS_VFF || d1.basis == VGGP_BASIS_B1) ? -1 : 1;
+    const int e2 = (d2.basis == VGGP_BASIS_VFF || d2.basis == VGGP_BASIS_B1) ? -1 : 1;
+    if ((rc = gemm1(d1.L0, m1, 1, w.a0, m2, 1, w.MkA1, (int)m2, (int)m1, (int)m2, (int)m1, st))) return rc;
+    if ((rc = gemm1(w.MkA1, m2, 1, d2.L0, 1, m2, mean, (int)m2, (int)m1, (int)m2, (int)m2, st))) return rc;
+    VGM_LAUNCH1D(vgm_scale_rho_kernel, M, st, mean, M, c->theta, e1, e2);
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+// posterior(x*) mean of the last iterative scattered step: (s1 s2 / v) u1^T A0 u2, u_d = L0_d^-1 a_d(x*_d), in chunks of points
+extern "C" int vggp_posterior_scattered_iter(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, void* stream) {
+    static const char* fn = "vggp_posterior_scattered_iter";
+    int rc = vgs_check(c, fn);
+    if (rc) return rc;
+    VG_REQUIRE(xs1 && xs2 && mean && ns >= 0, "%s: bad argument", fn);
+    if (!c->have_iter || !c->masked) { vg_set_error("%s: no finished vggp_elbo_step_scattered_iter on this context", fn); return VGGP_ESTATE; }
+    if (ns == 0) return VGGP_OK;
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const long m1 = w.m1, m2 = w.m2;
+    const long chunk = std::min<long>(ns, 1L << 16);
+    if ((rc = vg_ensure_misc(c, (size_t)chunk * (3 * m1 + 2 * m2) * sizeof(double)))) return rc;
+    double* p = (double*)c->misc;
+    double* A1 = p; p += m1 * chunk;
+    double* U1 = p; p += m1 * chunk;
+    double* T = p; p += m1 * chunk;
+    double* A2 = p; p += m2 * chunk;
+    double* U2 = p;
+    for (long off = 0; off < ns; off += chunk) {
+        const int cn = (int)std::min<long>(chunk, ns - off);
+        VgFactorJob fj[2] = {
+            VgFactorJob{xs1 + off, d1.grid, A1, nullptr, nullptr, nullptr, cn, d1.m, d1.kind, d1.basis, 0, 0.0, c->desc.flags},
+            VgFactorJob{xs2 + off, d2.grid, A2, nullptr, nullptr, nullptr, cn, d2.m, d2.kind, d2.basis, 1, 0.0, c->desc.flags}};
+        VG_HIP(vg_factor_build_launch(fj, 2, c->theta, st));
+        VgGemmBatch g;
+        vg_gemm_init(&g);
+        vg_gemm_add(&g, d1.Linv0, m1, 1, A1, cn, 1, U1, cn, (int)m1, cn, (int)m1);
+        vg_gemm_add(&g, d2.Linv0, m2, 1, A2, cn, 1, U2, cn, (int)m2, cn, (int)m2);
+        VG_HIP(vg_gemm_launch(&g, st));
+        if ((rc = gemm1(w.a0, m2, 1, U2, cn, 1, T, cn, (int)m1, cn, (int)m2, st))) return rc;                   // A0 U2
+        VGM_LAUNCH1D(vgm_coldot_kernel, cn, st, U1, T, (int)m1, (long)cn, mean + off);
+        VGM_LAUNCH1D(vgs_scale_mean_kernel, cn, st, mean + off, (long)cn, c->theta);
+    }
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+// building blocks, exported for tests: the two kernels of kr.hip on caller-supplied device arrays
+extern "C" int vggp_kr_field(vggp_ctx* c, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                             double* F, void* stream) {
+    if (!c) { vg_set_error("vggp_kr_field: null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(L && R && V && F, "vggp_kr_field: null argument");
+    VG_REQUIRE(m1 >= 1 && m1 <= 256 && m2 >= 1 && m2 <= 256 && nb >= 1 && nb <= 64 && N >= 1 && N < (1L << 24),
+               "vggp_kr_field: need 1 <= m_d <= 256, 1 <= nb <= 64, 1 <= N < 2^24");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VG_HIP(vg_kr_field_launch(L, R, V, (int)m1, (int)m2, (long)N, (int)nb, F, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+extern "C" int vggp_kr_back(vggp_ctx* c, const double* L, const double* R, const double* F, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                            double* out, void* stream) {
+    if (!c) { vg_set_error("vggp_kr_back: null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(L && R && F && out, "vggp_kr_back: null argument");
+    VG_REQUIRE(m1 >= 1 && m1 <= 256 && m2 >= 1 && m2 <= 256 && nb >= 1 && nb <= 64 && N >= 1 && N < (1L << 24),
+               "vggp_kr_back: need 1 <= m_d <= 256, 1 <= nb <= 64, 1 <= N < 2^24");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const size_t sc = vg_kr_back_scratch((int)m1, (int)m2, (long)N, (int)nb);
+    int rc = vg_ensure_misc(c, (sc + 32) * sizeof(double));
+    if (rc) return rc;
+    VG_HIP(vg_kr_back_launch(L, R, F, (int)m1, (int)m2, (long)N, (int)nb, out, (double*)c->misc, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
 }

@@ -273,6 +273,56 @@ class Engine:
                                                 _stream(self.device)))
         return elbo.value, np.array(list(grad)), self._info(info)
 
+    def elbo_step_scattered_iter(self, y: torch.Tensor, yy: float, theta: Sequence[float], n_probes: int = 16, tol: float = 1e-10,
+                                 max_iter: int = 100):
+        """The scattered step without any M x M matrix or m_d^2 x N buffer (PCG on the Khatri-Rao operator, Lanczos quadrature,
+        control-variate traces, fixed probes; include/vggp.h): any M with m_d <= 256.  -> (elbo, grad[5], info) with
+        info['rounds'][0] = PCG iterations.  Read-outs: qv_scattered_iter, posterior_scattered_iter (means only)."""
+        if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == self.n1):
+            raise TypeError("y must be a contiguous float64 GPU tensor with one value per planned point")
+        th = (C.c_double * 5)(*[float(t) for t in theta])
+        elbo = C.c_double()
+        grad = (C.c_double * 5)()
+        info = Info()
+        check(self.lib.vggp_elbo_step_scattered_iter(self._h, _ptr(y), float(yy), th, int(n_probes), float(tol), int(max_iter),
+                                                     C.byref(elbo), grad, C.byref(info), _stream(self.device)))
+        return elbo.value, np.array(list(grad)), self._info(info)
+
+    def qv_scattered_iter(self) -> torch.Tensor:
+        """q(v) mean [m1, m2] after elbo_step_scattered_iter (no solve; the variance is not provided yet)."""
+        mean = torch.empty(self.m1, self.m2, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_qv_scattered_iter(self._h, _ptr(mean), _stream(self.device)))
+        return mean
+
+    def posterior_scattered_iter(self, x_star: torch.Tensor) -> torch.Tensor:
+        """posterior(x*) mean after elbo_step_scattered_iter; x_star [ns, 2] -> mean [ns]."""
+        xs = x_star.to(self.device, torch.float64)
+        xs1, xs2 = xs[:, 0].contiguous(), xs[:, 1].contiguous()
+        ns = xs1.shape[0]
+        mean = torch.empty(ns, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_posterior_scattered_iter(self._h, _ptr(xs1), _ptr(xs2), ns, _ptr(mean), _stream(self.device)))
+        return mean
+
+    def kr_field(self, L: torch.Tensor, R: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
+        """Khatri-Rao field kernel: L [m1, N], R [m2, N], V [m1, nb, m2] -> F [nb, N], F[c, k] = l_k^T V_c r_k."""
+        m1, N = L.shape
+        m2, nb = R.shape[0], V.shape[1]
+        if R.shape[1] != N or tuple(V.shape) != (m1, nb, m2):
+            raise ValueError("kr_field: L [m1, N], R [m2, N], V [m1, nb, m2]")
+        F = torch.empty(nb, N, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_kr_field(self._h, _ptr(L), _ptr(R), _ptr(V), m1, m2, N, nb, _ptr(F), _stream(self.device)))
+        return F
+
+    def kr_back(self, L: torch.Tensor, R: torch.Tensor, F: torch.Tensor) -> torch.Tensor:
+        """Khatri-Rao back kernel: L [m1, N], R [m2, N], F [nb, N] -> out [m1, nb, m2] = sum_k F[c, k] l_k r_k^T."""
+        m1, N = L.shape
+        m2, nb = R.shape[0], F.shape[0]
+        if R.shape[1] != N or F.shape[1] != N:
+            raise ValueError("kr_back: L [m1, N], R [m2, N], F [nb, N]")
+        out = torch.empty(m1, nb, m2, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_kr_back(self._h, _ptr(L), _ptr(R), _ptr(F), m1, m2, N, nb, _ptr(out), _stream(self.device)))
+        return out
+
     def qv_masked(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> mean, var [m1, m2]; on a paired plan q(u) over the M inducing points, [M] each."""
         shape = (self.m1,) if self.paired else (self.m1, self.m2)

@@ -21,6 +21,7 @@ MultivariateNormal) are mirrored here only as far as the path reads them: parame
 from __future__ import annotations
 
 import math
+import warnings
 from typing import Optional, Tuple
 
 import numpy as np
@@ -196,15 +197,24 @@ class KroneckerStructure(torch.nn.Module):
     kind = "matern12"
 
     def __init__(self, X: torch.Tensor, y: torch.Tensor, engine: Optional[Engine] = None, warm_start: bool = True,
-                 solver: str = "auto"):
+                 solver: str = "auto", scattered_solver: str = "auto"):
         """solver: how a grid with holes is solved.  "dense": the M x M solver (M = m1 m2 <= 16384); "iterative": PCG without any
         M x M matrix (Engine.elbo_step_masked_iter and its read-outs; also accepted on a full grid, which it treats as a mask of
         ones); "auto": iterative only for a grid with holes whose M exceeds the dense solver's limit, dense everywhere else.
-        Scattered points and paired inducing points have no iterative solver: "iterative" raises ValueError there."""
+        `solver` does not apply to scattered points or paired inducing points: "iterative" raises ValueError there.
+        scattered_solver: how scattered points (along-track data) are solved.  "dense": the M x M solver (M <= 16384, four
+        m_d^2 x N buffers); "iterative": PCG on the Khatri-Rao operator without any of them (Engine.elbo_step_scattered_iter; q_v()
+        and posterior() then carry means only); "auto": iterative only when M exceeds the dense solver's limit ("iterative" on a grid
+        with holes, which `solver` governs otherwise, treats it as its observed points).  A model whose
+        inducing points are trained (SVGP, train_z=True) keeps the dense path: its Z-gradient reads dense state."""
         super().__init__()
         if solver not in ("auto", "dense", "iterative"):
             raise ValueError(f"solver must be 'auto', 'dense' or 'iterative', got {solver!r}")
+        if scattered_solver not in ("auto", "dense", "iterative"):
+            raise ValueError(f"scattered_solver must be 'auto', 'dense' or 'iterative', got {scattered_solver!r}")
         self.solver = solver
+        self.scattered_solver = scattered_solver
+        self._siter = False              # the iterative scattered step applies (decided at plan time)
         self.n_probes, self.tol, self.max_iter = 16, 1e-10, 100      # of the iterative solver (the engine's defaults)
         self._iter = False
         self.train_inputs = (X,)
@@ -239,6 +249,8 @@ class KroneckerStructure(torch.nn.Module):
         if self._scattered:
             self._no_iterative("scattered points")
         self._yy = float((yd * yd).sum().item()) if self._scattered else self._engine.sumsq(self._Y)
+        if scattered_solver == "iterative" and W is not None and not self._scattered:
+            self._as_scattered()         # forced on a grid with holes: it is then treated as its observed points
 
     def _no_iterative(self, what: str):
         if self.solver == "iterative":
@@ -250,6 +262,26 @@ class KroneckerStructure(torch.nn.Module):
         if self.solver == "dense" or self._scattered or not self._masked or basis == "paired":
             return False
         return self.solver == "iterative" or _basis_m(basis, np.asarray(g1)) * _basis_m(basis, np.asarray(g2)) > 16384
+
+    def _use_scattered_iterative(self, basis, g1, g2) -> bool:
+        """The iterative scattered solver applies (see __init__)."""
+        if not self._scattered or self.scattered_solver == "dense" or basis == "paired":
+            return False
+        want = self.scattered_solver == "iterative" or _basis_m(basis, np.asarray(g1)) * _basis_m(basis, np.asarray(g2)) > 16384
+        Z = getattr(self, "Z", None)
+        if want and isinstance(Z, torch.Tensor) and Z.requires_grad:
+            # vggp_zgrad_scattered reads the dense step's Sigma~^-1: trained inducing points stay on the dense path
+            if self.scattered_solver == "iterative" and not getattr(self, "_warned_siter", False):
+                warnings.warn(f"{type(self).__name__}: scattered_solver='iterative' does not apply while the inducing points are trained "
+                              f"(the Z-gradient reads the dense solver's state); the dense scattered solver is used")
+                self._warned_siter = True
+            return False
+        return want
+
+    def _scattered_iter_variance(self):
+        raise NotImplementedError(f"{type(self).__name__}: the iterative scattered solver provides means only; variances and covariances "
+                                  f"are a block PCG solve with the same operator and are the follow-up to vggp_qv_scattered_iter / "
+                                  f"vggp_posterior_scattered_iter (scattered_solver='dense' has them for M <= 16384)")
 
     def _as_scattered(self):
         """Switch a masked-grid model to the scattered representation of the same observations (one coordinate pair per point):
@@ -279,6 +311,7 @@ class KroneckerStructure(torch.nn.Module):
         factors, basis, meshes -- lives in the engine) or when its inducing description changed since the last plan."""
         basis, g1, g2 = self._basis()
         self._iter = self._use_iterative(basis, g1, g2)
+        self._siter = self._use_scattered_iterative(basis, g1, g2)
         key = (basis, np.asarray(g1).tobytes(), np.asarray(g2).tobytes())
         if self._planned and self._plan_token == self._engine.plan_token and key != self._plan_key and basis == "points" \
                 and self._plan_key is not None and len(self._plan_key[1]) == len(key[1]) and len(self._plan_key[2]) == len(key[2]):
@@ -289,7 +322,7 @@ class KroneckerStructure(torch.nn.Module):
                 self._engine.set_inducing(1, g2)
             self._plan_key = key
         elif not self._planned or self._plan_token != self._engine.plan_token or key != self._plan_key:
-            if (self._scattered or self._masked) and not self._iter:
+            if (self._scattered or self._masked) and not self._iter and not self._siter:
                 self._check_dense_workspace(basis, g1, g2)
             self._engine.plan(self.kind, basis, g1, self._x1, self.kind, basis, g2, self._x2, warm_start=self._warm,
                               b0_f32_kdelta=self._f32_mesh(), scattered=self._scattered)
@@ -306,7 +339,8 @@ class KroneckerStructure(torch.nn.Module):
         if M > 16384:
             raise ValueError(f"{type(self).__name__}: X is {'scattered' if self._scattered else 'a grid with holes'}, which takes the dense "
                              f"M-space solver, and M = m1 * m2 = {m1} * {m2} = {M} exceeds its limit of 16384 "
-                             f"(solver='auto' or 'iterative' handles larger M on grids with holes)")
+                             f"(solver='auto' or 'iterative' handles larger M on grids with holes, scattered_solver='auto' or "
+                             f"'iterative' on scattered points whose inducing points are not trained)")
         n_pair = N if self._scattered else max(len(self._x1), len(self._x2))
         need = 8.0 * (10.0 * M * M + 2.0 * (m1 * m1 + m2 * m2) * n_pair)
         free = torch.cuda.mem_get_info(self._engine.device)[0] if torch.cuda.is_available() else None
@@ -322,6 +356,9 @@ class KroneckerStructure(torch.nn.Module):
 
     def _engine_step(self, theta):
         self._plan()
+        if self._siter:
+            return self._engine.elbo_step_scattered_iter(self._Y, self._yy, theta, n_probes=self.n_probes, tol=self.tol,
+                                                         max_iter=self.max_iter)
         if self._scattered:
             return self._engine.elbo_step_scattered(self._Y, self._yy, theta)
         if self._iter:
@@ -345,6 +382,9 @@ class KroneckerStructure(torch.nn.Module):
         """gridded_kronecker_structure.py:1409-1433 == kronecker_structure.py:825-849.
         mean is flat (M,) with u = i1*m2 + i2 (callers do `.mean.reshape(m, m).T`)."""
         self._refresh()
+        if self._siter:                  # iterative scattered solver: the mean only (no solve)
+            return MultivariateNormal(self._engine.qv_scattered_iter().reshape(-1).cpu(), self._scattered_iter_variance,
+                                      cov_fn=self._scattered_iter_variance)
         if self._iter:
             # iterative solver: the mean needs no solve and comes now; the variance of all M cells costs ceil(M / 64) block PCG
             # solves and is computed on first use (q_v_at gives it for a few cells); there is no dense covariance
@@ -379,6 +419,9 @@ class KroneckerStructure(torch.nn.Module):
         N* x N* matrix, :223-229) is materialised on first access (vggp_posterior_cov: N* <= 8192, M N* <= 2^27)."""
         self._refresh()
         xs = torch.as_tensor(x_star, dtype=torch.float64)
+        if self._siter:
+            return MultivariateNormal(self._engine.posterior_scattered_iter(xs).cpu(), self._scattered_iter_variance,
+                                      cov_fn=self._scattered_iter_variance)
         if self._iter:                   # (no dense covariance on the iterative solver: .covariance_matrix raises)
             mean, var, _ = self._engine.posterior_masked_iter(xs, self._W, self._nobs, tol=self.tol, max_iter=self.max_iter)
             return MultivariateNormal(mean.cpu(), var.cpu())
@@ -555,6 +598,9 @@ class Matern12VFFGP(KroneckerStructure):
 
 
 def _no_gridded_readout(model):
+    if model._siter:
+        raise NotImplementedError(f"{type(model).__name__}: the gridded read-out q_v() is not available on the iterative scattered solver "
+                                  f"(q_u() and posterior() means are)")
     if model._iter:
         raise NotImplementedError(f"{type(model).__name__}: the gridded read-out q_v() is not available on the iterative masked solver "
                                   f"(q_u(), q_v_at() on the inducing features and posterior() are)")
