@@ -245,8 +245,9 @@ int vggp_posterior_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, con
 int vggp_elbo_step_scattered_iter(vggp_ctx* ctx, const double* y, double yy, const double theta[5], int n_probes, double tol,
                                   int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream);
 /* Mean read-outs of the iterative scattered step; both need only a0: mean = (s1 s2 / sigma^2) t^T a0.  VGGP_ESTATE unless the LAST
- * finished step on the context was a successful vggp_elbo_step_scattered_iter.  VARIANCES ARE NOT PROVIDED YET: they are one block
- * PCG solve with the same operator (as vggp_qv_masked_iter does for grids) and are the follow-up to these entries.
+ * finished step on the context was a successful vggp_elbo_step_scattered_iter.  The POINT-WISE VARIANCES of these two are not provided
+ * yet: they are block PCG solves with the same operator (the one vggp_readout_scattered_iter below runs for grid cells) and are the
+ * follow-up to these entries.
  *   vggp_qv_scattered_iter         mean DEVICE [m1][m2] = L0_1 A0 L0_2^T scaled as vggp_qv_masked_iter scales it (e_d = -1 for VFF / B1)
  *   vggp_posterior_scattered_iter  xs1, xs2 DEVICE [n_star]; mean DEVICE [n_star] */
 int vggp_qv_scattered_iter(vggp_ctx* ctx, double* mean, void* stream);
@@ -259,6 +260,35 @@ int vggp_kr_field(vggp_ctx* ctx, const double* L, const double* R, const double*
                   double* F, void* stream);
 int vggp_kr_back(vggp_ctx* ctx, const double* L, const double* R, const double* F, int64_t m1, int64_t m2, int64_t N, int64_t nb,
                  double* out, void* stream);
+/* Gridded read-out q(v) of B0 cell features after an ITERATIVE step: vggp_readout_masked's algebra and scaling (C_d DEVICE [mv_d][m_d],
+ * kd_d DEVICE [mv_d], flags = VGGP_READOUT_LITERAL as there) with Sigma~^-1 applied instead of stored, so M = m1 m2 is not limited.
+ * U_d = L0_d^-1 C_d^T; cell (a, b) owns t = U1[:, a] (x) U2[:, b]; rho = s1 s2 / sigma^2; P_d = U_d^T B_d (mv_d x n_d).
+ *   mean      rho U1^T A0 U2, all cells, two GEMMs, no solve
+ *   literal   var[a][b] = s1 s2 (kd1[a] kd2[b] + rho S[a][b]): the reference's expression (X = S_u^-1), where |t|^2 cancels and
+ *             t^T Sigma~ t is a Gram product over the data -- S = (P1 o P1)(P2 o P2)^T over the points (vggp_kr_sqgram on chunks of
+ *             points, workspace O((mv1 + mv2) chunk + mv1 mv2) whatever N) or (P1 o P1) W^T (P2 o P2)^T on a grid with holes.  No solve:
+ *             all cells for about one application of the operator; info->sweeps1 = 0
+ *   otherwise var = s1 s2 (kd1[a] kd2[b] - |t|^2 + t^T Sigma~^-1 t), the conditional variance under q(u): block PCG solves over `block`
+ *             cells at a time as vggp_qv_masked_iter runs them (operator, kept preconditioner basis, per-column stopping rule; no
+ *             probes); info->rounds1 = largest PCG count, info->sweeps1 = number of block solves
+ *   mean   DEVICE [mv1][mv2], every cell (NULL to skip)
+ *   cells  HOST int64 [n_cells] flat indices a*mv2 + b, or NULL with n_cells = mv1*mv2 for every cell
+ *   var    DEVICE [n_cells] (NULL with n_cells = 0: the mean only)
+ *   W, n_obs (masked), tol, max_iter, block: as vggp_qv_masked_iter
+ * VGGP_ESTATE unless the LAST finished step on the context was the matching successful iterative step; VGGP_ENOCONV when a column does
+ * not converge; VGGP_EINVAL on paired or multi-rank contexts, the wrong plan kind (a grid against VGGP_FLAG_SCATTERED), a cell index
+ * outside [0, mv1*mv2), block > 64.  The block solve's workspace is the iterative read-outs' (allocated on first use, apart from the
+ * step's): a read-out leaves the kept preconditioner basis valid and the next step's results unchanged. */
+int vggp_readout_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, const double* C1, int64_t mv1, const double* C2, int64_t mv2,
+                             const double* kd1, const double* kd2, const int64_t* cells, int64_t n_cells, double tol, int max_iter,
+                             int block, double* mean, double* var, int flags, vggp_info* info, void* stream);
+int vggp_readout_scattered_iter(vggp_ctx* ctx, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1,
+                                const double* kd2, const int64_t* cells, int64_t n_cells, double tol, int max_iter, int block,
+                                double* mean, double* var, int flags, vggp_info* info, void* stream);
+/* Building block of the literal read-out, exported for tests: out[a][b] = sum_k P1[a][k]^2 P2[b][k]^2 on DEVICE arrays P1 [mv1][N],
+ * P2 [mv2][N], out [mv1][mv2]; any mv_d >= 1 (mv1 mv2 < 2^28).  An fp64-MFMA GEMM whose operands are squared as its fragments are
+ * formed; reduction split over workgroups, slabs summed in fixed order: bitwise reproducible.  The context need not be planned. */
+int vggp_kr_sqgram(vggp_ctx* ctx, const double* P1, const double* P2, int64_t mv1, int64_t mv2, int64_t N, double* out, void* stream);
 /* q(v) of the last masked step: mean and covariance diagonal, DEVICE [m1][m2]. */
 int vggp_qv_masked(vggp_ctx* ctx, double* mean, double* var, void* stream);
 /* posterior(x*) of the last masked step (kronecker_structure.py:199-230); arguments as vggp_posterior. */

@@ -68,6 +68,11 @@ SYMBOLS = {
     "vggp_posterior_scattered_iter": (_I, [_P, _P, _P, _I64, _P, _P]),
     "vggp_kr_field": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "vggp_kr_back": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "vggp_readout_masked_iter": (_I, [_P, _P, _D, _P, _I64, _P, _I64, _P, _P, C.POINTER(_I64), _I64, _D, _I, _I, _P, _P, _I,
+                                      C.POINTER(Info), _P]),
+    "vggp_readout_scattered_iter": (_I, [_P, _P, _I64, _P, _I64, _P, _P, C.POINTER(_I64), _I64, _D, _I, _I, _P, _P, _I,
+                                         C.POINTER(Info), _P]),
+    "vggp_kr_sqgram": (_I, [_P, _P, _P, _I64, _I64, _I64, _P, _P]),
     "vggp_qv_masked": (_I, [_P, _P, _P, _P]),
     "vggp_qv": (_I, [_P, _P, _P, _P]),
     "vggp_qv_cov": (_I, [_P, _P, _P]),

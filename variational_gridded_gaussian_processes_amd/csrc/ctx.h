@@ -175,6 +175,10 @@ hipError_t vg_kr_field_launch(const double* L, const double* R, const double* V,
 size_t vg_kr_back_scratch(int m1, int m2, long N, int nb);      // doubles of split scratch vg_kr_back_launch needs (bounded whatever N)
 hipError_t vg_kr_back_launch(const double* L, const double* R, const double* F, int m1, int m2, long N, int nb, double* out, double* scratch,
                              hipStream_t st);
+// out [mv1][mv2] (+)= sum_k P1[a][k]^2 P2[b][k]^2, P_d [mv_d][N]; scratch: vg_kr_sqgram_scratch doubles (unused when that is mv1 mv2 and !accum)
+size_t vg_kr_sqgram_scratch(int mv1, int mv2, long N);
+hipError_t vg_kr_sqgram_launch(const double* P1, const double* P2, int mv1, int mv2, long N, double* out, double* scratch, int accum,
+                               hipStream_t st);
 // batch of triangular solves, each in place on its X (api.hip trsm_batch: element (row k, column c) at X[k * sk + c * sc])
 #define VG_TRSM_BLK 128
 struct VgTrsmSpec {

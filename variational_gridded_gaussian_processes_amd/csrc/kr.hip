@@ -278,3 +278,144 @@ hipError_t vg_kr_back_launch(const double* L, const double* R, const double* F, 
     vg_red_add(&r, scratch, out, a.slab, a.slab, ks);
     return vg_red_launch(&r, st);
 }
+
+// ---- squared Gram product of the gridded read-out (vggp_readout_scattered_iter, literal variance) -------------------------------------
+//     out[a][b] = sum_k P1[a][k]^2 P2[b][k]^2          P1 [mv1][N], P2 [mv2][N], any mv_d >= 1
+// The back kernel's GEMM with one column and F = 1: 64 x 64 tiles, 16-deep k-tiles, both operands k-contiguous ([row][BK + 1] in LDS),
+// the operands squared as the fragments are read from LDS (no squared copy exists) and two register stages in flight as in
+// gemm_body.h.  The reduction over the points is split over workgroups when the output has few tiles; the slabs are summed in fixed
+// order (and, with accum, on top of what out already holds -- the chunks of a long point list): no atomics, bitwise reproducible.
+struct VgKrSqArgs {
+    const double* P1;
+    const double* P2;
+    double* out;          // slab s at out + s * slab
+    long N, slab;
+    int mv1, mv2, kchunk, tiles_a, tiles_b;
+};
+
+__global__ __launch_bounds__(256) void vg_kr_sqgram_kernel(const VgKrSqArgs A) {
+    __shared__ double As[VG_KR_T * VG_KR_RS];
+    __shared__ double Bs[VG_KR_T * VG_KR_RS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int fi = lane & 15, fk = lane >> 4;
+    const int mv1 = A.mv1, mv2 = A.mv2;
+    const long N = A.N;
+    int t = blockIdx.x;
+    const int tb = t % A.tiles_b; t /= A.tiles_b;
+    const int ta = t % A.tiles_a; t /= A.tiles_a;
+    const int ks = t;
+    const long kb = (long)ks * A.kchunk;
+    const long ke = kb + A.kchunk < N ? kb + A.kchunk : N;
+    const int nkt = ke > kb ? (int)((ke - kb + VG_KR_BK - 1) / VG_KR_BK) : 0;
+    const int s_k = tid & 15, s_i = tid >> 4;              // both tiles are k-contiguous: rows s_i + 16 r
+    const double* pa[4];
+    const double* pb[4];
+    bool aok[4], bok[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int ga = ta * VG_KR_T + s_i + 16 * r, gb = tb * VG_KR_T + s_i + 16 * r;
+        aok[r] = ga < mv1; bok[r] = gb < mv2;
+        pa[r] = A.P1 + (long)(aok[r] ? ga : mv1 - 1) * N;
+        pb[r] = A.P2 + (long)(bok[r] ? gb : mv2 - 1) * N;
+    }
+    double ra0[4], rb0[4], ra1[4], rb1[4];
+    auto load = [&](int kt, double (&ra)[4], double (&rb)[4]) {
+        const long gk = kb + (long)kt * VG_KR_BK + s_k;
+        const bool kok = gk < ke;
+        const long gkc = kok ? gk : ke - 1;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double l = pa[r][gkc], w = pb[r][gkc];
+            ra[r] = (kok && aok[r]) ? l : 0.0;
+            rb[r] = (kok && bok[r]) ? w : 0.0;
+        }
+    };
+    vg_d4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (vg_d4){0.0, 0.0, 0.0, 0.0};
+    auto ktile = [&](double (&ra)[4], double (&rb)[4], int knext) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            As[(s_i + 16 * r) * VG_KR_RS + s_k] = ra[r];
+            Bs[(s_i + 16 * r) * VG_KR_RS + s_k] = rb[r];
+        }
+        __syncthreads();
+        if (knext < nkt) load(knext, ra, rb);                 // refill this stage: two k-tiles ahead
+#pragma unroll
+        for (int kk = 0; kk < VG_KR_BK; kk += 4) {
+            double av[2], bv[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const double v = As[(wr * 32 + i * 16 + fi) * VG_KR_RS + kk + fk];
+                av[i] = v * v;                                // the operands P1^2, P2^2, formed here
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const double v = Bs[(wc * 32 + j * 16 + fi) * VG_KR_RS + kk + fk];
+                bv[j] = v * v;
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[i], bv[j], acc[i][j], 0, 0, 0);
+        }
+        __syncthreads();
+    };
+    if (nkt > 0) load(0, ra0, rb0);
+    if (nkt > 1) load(1, ra1, rb1);
+    for (int kt = 0; kt < nkt; kt += 2) {
+        ktile(ra0, rb0, kt + 2);
+        if (kt + 1 < nkt) ktile(ra1, rb1, kt + 3);
+    }
+    double* out = A.out + (long)ks * A.slab;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int a = ta * VG_KR_T + wr * 32 + i * 16 + fk + 4 * r;
+                const int b = tb * VG_KR_T + wc * 32 + j * 16 + fi;
+                if (a < mv1 && b < mv2) out[(long)a * mv2 + b] = acc[i][j][r];
+            }
+}
+
+// out[i] = (accum ? out[i] : 0) + slab 0 + slab 1 + ...   (fixed order, as vg_red_kernel)
+__global__ __launch_bounds__(256) void vg_kr_sqred_kernel(const double* in, double* out, long n, int nslab, int accum) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    double v = in[i];
+    for (int k = 1; k < nslab; ++k) v += in[(long)k * n + i];
+    out[i] = accum ? out[i] + v : v;
+}
+
+static int kr_sq_split(int mv1, int mv2, long N) {          // as kr_back_split: ~4 workgroups per CU, slabs of at least 256 points
+    const long wg = (long)((mv1 + VG_KR_T - 1) / VG_KR_T) * ((mv2 + VG_KR_T - 1) / VG_KR_T);
+    long ks = (1024 + wg - 1) / wg;
+    if (ks > VG_KR_MAXSPLIT) ks = VG_KR_MAXSPLIT;
+    if (ks > N / 256) ks = N / 256;
+    return ks < 1 ? 1 : (int)ks;
+}
+size_t vg_kr_sqgram_scratch(int mv1, int mv2, long N) {     // doubles; at most (1024 / tiles + 1) * mv1 * mv2 whatever N
+    return (size_t)kr_sq_split(mv1, mv2, N) * mv1 * mv2;
+}
+hipError_t vg_kr_sqgram_launch(const double* P1, const double* P2, int mv1, int mv2, long N, double* out, double* scratch, int accum,
+                               hipStream_t st) {
+    VgKrSqArgs a{};
+    a.P1 = P1; a.P2 = P2; a.N = N; a.mv1 = mv1; a.mv2 = mv2;
+    a.tiles_a = (mv1 + VG_KR_T - 1) / VG_KR_T; a.tiles_b = (mv2 + VG_KR_T - 1) / VG_KR_T;
+    int ks = kr_sq_split(mv1, mv2, N);
+    const long chunk = ((N + ks - 1) / ks + VG_KR_BK - 1) / VG_KR_BK * VG_KR_BK;
+    ks = (int)((N + chunk - 1) / chunk);
+    a.kchunk = (int)chunk;
+    a.slab = (long)mv1 * mv2;
+    const bool direct = ks == 1 && !accum;
+    a.out = direct ? out : scratch;
+    hipLaunchKernelGGL(vg_kr_sqgram_kernel, dim3((unsigned)(a.tiles_a * a.tiles_b * ks)), dim3(256), 0, st, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || direct) return e;
+    hipLaunchKernelGGL(vg_kr_sqred_kernel, dim3((unsigned)((a.slab + 255) / 256)), dim3(256), 0, st, scratch, out, a.slab, ks, accum);
+    return hipGetLastError();
+}

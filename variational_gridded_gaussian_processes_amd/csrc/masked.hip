@@ -1647,6 +1647,7 @@ struct VgReadout {
     double *T;                  // the right-hand sides, kept for the reductions
     double *A1, *A2, *U1, *U2;  // posterior(x*): factor columns a_d(x*) and U_d = L0_d^-1 a_d  [m_d][cn]
     long long* cells;           // q(v): this block's flat cell indices
+    double* krs;                // scattered: split scratch of the back kernel
 };
 
 // T[a][c][b] = U1[a][c] U2[b][c] for the cn columns of this block (U_d: [m_d][cn]); the unused columns of a ragged block are zero
@@ -1703,6 +1704,7 @@ static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post) {
     size_t off = 0;
     char* base = nullptr;
     VgIter& it = r.it;
+    const bool sc = w.scattered;          // scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N]
     for (int pass = 0; pass < 2; ++pass) {
         off = 0;
         auto take = [&](size_t count) {
@@ -1711,16 +1713,17 @@ static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post) {
             off += count * sizeof(double);
             return p;
         };
-        it.Wt = take(n1 * n2);
+        it.Wt = take(sc ? 0 : n1 * n2);
         it.X = take(M * nbc); it.R = take(M * nbc); it.Zp = take(M * nbc); it.Pd = take(M * nbc); it.AP = take(M * nbc);
         it.Tm = take(M * nbc); it.Tm2 = take(M * nbc); r.T = take(M * nbc);
-        it.T1 = take(n1 * nbc * mx);
-        it.F0 = take(n1 * nbc * n2);
+        it.T1 = take(sc ? 0 : n1 * nbc * mx);
+        it.F0 = take(sc ? n1 * nbc : n1 * nbc * n2);
         it.alh = take((size_t)nbc); it.beh = take((size_t)nbc);
         it.col = take(8 * (size_t)nbc);
         r.A1 = take(post ? m1 * nbc : 0); r.A2 = take(post ? m2 * nbc : 0);
         r.U1 = take(post ? m1 * nbc : 0); r.U2 = take(post ? m2 * nbc : 0);
         r.cells = reinterpret_cast<long long*>(take((size_t)nbc));
+        r.krs = take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
         it.nact = reinterpret_cast<int*>(take(8));
         if (pass == 0) {
             const size_t need = off + 4096;
@@ -1728,7 +1731,7 @@ static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post) {
                 if (w.rmem) { VG_HIP(hipFree(w.rmem)); w.rmem = nullptr; w.rbytes = 0; }
                 size_t free_b = 0, total_b = 0;
                 if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-                    vg_set_error("the read-out workspace of the iterative masked step needs %.1f GiB at block = %d but only %.1f GiB of device "
+                    vg_set_error("the read-out workspace of the iterative step needs %.1f GiB at block = %d but only %.1f GiB of device "
                                  "memory are free (a smaller block needs less)", (double)need / 1073741824.0, nbc, (double)free_b / 1073741824.0);
                     return VGGP_ENOMEM;
                 }
@@ -1742,7 +1745,8 @@ static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post) {
     return VGGP_OK;
 }
 
-// Sigma~ X = T for the block in r.T: the step's PCG loop without the coefficient history (zero columns start inactive)
+// Sigma~ X = T for the block in r.T: the step's PCG loop without the coefficient history (zero columns start inactive).  A function of
+// (the step's operands, r.T) -> r.it.X for either data kind: the masked Kronecker operator, or the Khatri-Rao one with p = 1 / N
 static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, double tol, int max_iter, int* iters_out, int* nact_out,
                              hipStream_t st) {
     VgIter& it = r.it;
@@ -1759,9 +1763,14 @@ static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, d
     hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
     int iters = 0, nact = nbc;
     for (int k = 0; k < max_iter && nact > 0; ++k) {
-        if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
-        VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
-        if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
+        if (w.scattered) {               // the Khatri-Rao operator of the scattered step (n1 points)
+            VG_HIP(vg_kr_field_launch(B1, B2, it.Pd, (int)m1, (int)m2, n1, nbc, it.F0, st));
+            VG_HIP(vg_kr_back_launch(B1, B2, it.F0, (int)m1, (int)m2, n1, nbc, it.AP, r.krs, st));
+        } else {
+            if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
+            VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
+            if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
+        }
         VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
         hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
                            (int)m2, it.col + nbc, (double*)nullptr);
@@ -2312,4 +2321,222 @@ extern "C" int vggp_kr_back(vggp_ctx* c, const double* L, const double* R, const
     VG_HIP(vg_kr_back_launch(L, R, F, (int)m1, (int)m2, (long)N, (int)nb, out, (double*)c->misc, st));
     VG_HIP(hipStreamSynchronize(st));
     return VGGP_OK;
+}
+extern "C" int vggp_kr_sqgram(vggp_ctx* c, const double* P1, const double* P2, int64_t mv1, int64_t mv2, int64_t N, double* out, void* stream) {
+    if (!c) { vg_set_error("vggp_kr_sqgram: null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(P1 && P2 && out, "vggp_kr_sqgram: null argument");
+    VG_REQUIRE(mv1 >= 1 && mv2 >= 1 && mv1 < (1L << 20) && mv2 < (1L << 20) && mv1 * mv2 < (1L << 28) && N >= 1 && N < (1L << 31) - 64,
+               "vggp_kr_sqgram: need mv_d >= 1, mv1 mv2 < 2^28, 1 <= N < 2^31");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    int rc = vg_ensure_misc(c, (vg_kr_sqgram_scratch((int)mv1, (int)mv2, (long)N) + 32) * sizeof(double));
+    if (rc) return rc;
+    VG_HIP(vg_kr_sqgram_launch(P1, P2, (int)mv1, (int)mv2, (long)N, out, (double*)c->misc, 0, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+// ================================================================================================================================
+// Gridded read-out q(v) of B0 cell features after an ITERATIVE step (vggp_readout_masked_iter, vggp_readout_scattered_iter): the
+// algebra and scaling of vggp_readout_masked with Sigma~^-1 applied instead of stored.  U_d = L0_d^-1 C_d^T (m_d x mv_d); cell (a, b)
+// owns the rank-one column t = U1[:, a] (x) U2[:, b];  rho = s1 s2 / sigma^2.
+//   mean       rho U1^T A0 U2 for all cells: two GEMMs on the a0 the step left, no solve
+//   literal    var = s1 s2 (kd1_a kd2_b - |t|^2 + t^T Sigma~ t): the |t|^2 cancel and t^T Phi t is a Gram product over the data,
+//                  var[a][b] = s1 s2 (kd1[a] kd2[b] + rho S[a][b]),   P_d = U_d^T B_d (mv_d x n_d)
+//                  scattered   S = (P1 o P1)(P2 o P2)^T over the N points: vg_kr_sqgram on chunks of points (P_d exists for one chunk only;
+//                              the partial S are accumulated in chunk order)
+//                  masked      S = (P1 o P1) W^T (P2 o P2)^T: two of the step's GEMMs on the squared P_d
+//              no solve (info->sweeps1 = 0), all cells for about one operator application
+//   conditional var = s1 s2 (kd1_a kd2_b - |t|^2 + t^T Sigma~^-1 t): block PCG solves Sigma~ X = T (vgi_readout_solve) over `block` <= 64
+//              cells at a time, deterministic
+// Specification: tests/gridded_iter_readout_spec.py.
+// ================================================================================================================================
+// T[i][c][j] = U1[i][a_c] U2[j][b_c], cell p_c = cells[c] (or p0 + c) = a mv2 + b; the unused columns of a ragged block are zero
+__global__ void vgi_rank1_grid_kernel(const double* U1, const double* U2, const long long* cells, long p0, int m1, int nbc, int m2, long mv1,
+                                      long mv2, int cn, double* T) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)m1 * nbc * m2) return;
+    const int j = (int)(idx % m2), c = (int)((idx / m2) % nbc), i = (int)(idx / ((long)m2 * nbc));
+    if (c >= cn) { T[idx] = 0.0; return; }
+    const long p = cells ? (long)cells[c] : p0 + c;
+    const long a = p / mv2, b = p - a * mv2;
+    T[idx] = U1[(long)i * mv1 + a] * U2[(long)j * mv2 + b];
+}
+// one workgroup per column (vgi_readout_reduce_kernel with kd1[a] kd2[b] in place of kappa): var = s1 s2 (kd1_a kd2_b - <T,T> + <T,X>)
+__global__ __launch_bounds__(256) void vgi_readout_reduce_grid_kernel(const double* T, const double* X, int m1, int nbc, int m2,
+                                                                      const double* theta, const double* kd1, const double* kd2,
+                                                                      const long long* cells, long p0, long mv2, double* var) {
+    __shared__ double red[8];
+    const int c = blockIdx.x;
+    double nrm = 0.0, quad = 0.0;
+    for (long e = threadIdx.x; e < (long)m1 * m2; e += 256) {
+        const long a = e / m2, b = e - a * m2, o = (a * nbc + c) * m2 + b;
+        const double t = T[o];
+        nrm += t * t;
+        quad += t * X[o];
+    }
+    for (int off = 32; off > 0; off >>= 1) { nrm += __shfl_xor(nrm, off); quad += __shfl_xor(quad, off); }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = nrm; red[4 + (threadIdx.x >> 6)] = quad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        nrm = (red[0] + red[1]) + (red[2] + red[3]);
+        quad = (red[4] + red[5]) + (red[6] + red[7]);
+        const long p = cells ? (long)cells[c] : p0 + c;
+        const long a = p / mv2, b = p - a * mv2;
+        var[c] = theta[2] * theta[3] * (kd1[a] * kd2[b] - nrm + quad);
+    }
+}
+// literal: var[q] = s1 s2 (kd1[a] kd2[b] + rho S[a][b]) at cell p = cells[q] (or q)
+__global__ void vgi_readout_literal_kernel(const double* S, const double* kd1, const double* kd2, const double* theta, const long long* cells,
+                                           long mv2, long n, double* var) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const long p = cells ? (long)cells[q] : q;
+    const long a = p / mv2, b = p - a * mv2;
+    const double ss = theta[2] * theta[3];
+    var[q] = ss * (kd1[a] * kd2[b] + (ss / theta[4]) * S[p]);
+}
+
+static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, const double* C1, int64_t mv1,
+                           const double* C2, int64_t mv2, const double* kd1, const double* kd2, const int64_t* cells, int64_t n_cells,
+                           double tol, int max_iter, int block, double* mean, double* var, int flags, vggp_info* info, void* stream) {
+    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
+    VG_NOT_PAIRED(c, fn);
+    if (scattered) VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: the context was planned for a grid (vggp_readout_masked_iter reads those)", fn);
+    else VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: the context was planned for scattered points (vggp_readout_scattered_iter reads those)", fn);
+    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
+    const long m1 = c->desc.m1, m2 = c->desc.m2, n1 = c->desc.n1, n2 = c->desc.n2, M = m1 * m2;
+    VG_REQUIRE(C1 && C2 && kd1 && kd2 && mv1 > 0 && mv2 > 0 && mv1 < (1L << 20) && mv2 < (1L << 20) && mv1 * mv2 < (1L << 28) && n_cells >= 0,
+               "%s: bad argument (C_d, kd_d non-null, mv_d >= 1, mv1 mv2 < 2^28)", fn);
+    const long ncell_all = mv1 * mv2;
+    if (!scattered) VG_REQUIRE(W && std::isfinite(n_obs) && n_obs > 0.0, "%s: bad argument (W, n_obs)", fn);
+    VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
+    VG_REQUIRE((n_cells == 0 && !var) || (n_cells > 0 && var), "%s: var and n_cells must be given together (NULL with 0: mean only)", fn);
+    VG_REQUIRE(mean || var, "%s: nothing to compute (mean and var are NULL)", fn);
+    VG_REQUIRE(cells || n_cells == 0 || n_cells == ncell_all, "%s: cells = NULL means every cell: n_cells must be mv1 mv2 = %ld", fn, ncell_all);
+    if (cells)
+        for (int64_t k = 0; k < n_cells; ++k)
+            VG_REQUIRE(cells[k] >= 0 && cells[k] < ncell_all, "%s: cells[%lld] = %lld is outside [0, mv1 mv2 = %ld)", fn, (long long)k,
+                       (long long)cells[k], ncell_all);
+    auto fits = [&](long b) {
+        return scattered ? (n1 * b < (1L << 31) && M * b < (1L << 31)) : (n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31));
+    };
+    if (block <= 0) { block = 64; while (block > 1 && !fits(block)) block >>= 1; }
+    VG_REQUIRE(fits(block), "%s: problem too large for block = %d", fn, block);
+    if (!c->have_iter || !c->masked) {
+        vg_set_error("%s: no finished %s on this context", fn, scattered ? "vggp_elbo_step_scattered_iter" : "vggp_elbo_step_masked_iter");
+        return VGGP_ESTATE;
+    }
+    if (max_iter <= 0) max_iter = 100;
+    if (!(tol > 0.0)) tol = 1e-10;
+    if (info) { info->jitter1 = info->jitter2 = 0.0; info->sweeps1 = info->sweeps2 = info->rounds1 = info->rounds2 = 0; info->status = 0; info->polished = 0; }
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const double *B1 = d1.BV, *B2 = d2.BV;
+    const bool literal = (flags & VGGP_READOUT_LITERAL) != 0;
+    const bool lit = literal && n_cells > 0;
+    // the literal path forms P_d = U_d^T B_d for `chunk` points (scattered) / the n_d grid nodes (masked) at a time
+    long chunk = 0;
+    if (lit && scattered) {
+        chunk = std::min<long>(n1, 1L << 16);
+        while ((mv1 + mv2) * chunk > (1L << 25) && chunk > 4096) chunk >>= 1;
+    }
+    const long np1 = lit ? (scattered ? chunk : n1) : 0, np2 = lit ? (scattered ? chunk : n2) : 0;
+    const size_t sq = lit && scattered ? vg_kr_sqgram_scratch((int)mv1, (int)mv2, chunk) : 0;
+    size_t need = 0;
+    auto room = [&](size_t count) { const size_t o = need; need += (count + 31) & ~size_t(31); return o; };
+    const size_t oU1 = room(m1 * mv1), oU2 = room(m2 * mv2), oTm = room(mv1 * std::max(m2, lit && !scattered ? n2 : 0L));
+    const size_t oCells = room(cells ? (size_t)n_cells : 0);
+    const size_t oP1 = room(mv1 * np1), oP2 = room(mv2 * np2), oS = room(lit ? ncell_all : 0), oSq = room(sq);
+    int rc = vg_ensure_misc(c, need * sizeof(double));
+    if (rc) return rc;
+    double* base = (double*)c->misc;
+    double *U1 = base + oU1, *U2 = base + oU2, *Tm = base + oTm, *P1 = base + oP1, *P2 = base + oP2, *S = base + oS, *Sq = base + oSq;
+    long long* dcells = cells ? reinterpret_cast<long long*>(base + oCells) : nullptr;
+    if (cells && n_cells > 0) VG_HIP(hipMemcpyAsync(dcells, cells, sizeof(long long) * n_cells, hipMemcpyHostToDevice, st));
+    {   // U_d = Linv0_d C_d^T   (m_d x mv_d)
+        VgGemmBatch g;
+        vg_gemm_init(&g);
+        vg_gemm_add(&g, d1.Linv0, m1, 1, C1, 1, m1, U1, (int)mv1, (int)m1, (int)mv1, (int)m1);
+        vg_gemm_add(&g, d2.Linv0, m2, 1, C2, 1, m2, U2, (int)mv2, (int)m2, (int)mv2, (int)m2);
+        VG_HIP(vg_gemm_launch(&g, st));
+    }
+    if (mean) {          // rho U1^T A0 U2
+        if ((rc = gemm1(U1, 1, mv1, w.a0, m2, 1, Tm, (int)m2, (int)mv1, (int)m2, (int)m1, st))) return rc;
+        if ((rc = gemm1(Tm, m2, 1, U2, mv2, 1, mean, (int)mv2, (int)mv1, (int)mv2, (int)m2, st))) return rc;
+        VGM_LAUNCH1D(vgs_scale_mean_kernel, ncell_all, st, mean, ncell_all, c->theta);
+        VG_HIP(hipGetLastError());
+    }
+    if (n_cells == 0) { VG_HIP(hipStreamSynchronize(st)); return VGGP_OK; }
+    if (literal) {
+        if (scattered) {
+            for (long off = 0; off < n1; off += chunk) {
+                const long cn = std::min<long>(chunk, n1 - off);
+                VgGemmBatch g;
+                vg_gemm_init(&g);          // P_d[:, chunk] = U_d^T B_d[:, chunk]
+                vg_gemm_add(&g, U1, 1, mv1, B1 + off, n1, 1, P1, (int)cn, (int)mv1, (int)cn, (int)m1);
+                vg_gemm_add(&g, U2, 1, mv2, B2 + off, n1, 1, P2, (int)cn, (int)mv2, (int)cn, (int)m2);
+                VG_HIP(vg_gemm_launch(&g, st));
+                VG_HIP(vg_kr_sqgram_launch(P1, P2, (int)mv1, (int)mv2, cn, S, Sq, off > 0 ? 1 : 0, st));
+            }
+        } else {
+            VgGemmBatch g;
+            vg_gemm_init(&g);
+            vg_gemm_add(&g, U1, 1, mv1, B1, n1, 1, P1, (int)n1, (int)mv1, (int)n1, (int)m1);
+            vg_gemm_add(&g, U2, 1, mv2, B2, n2, 1, P2, (int)n2, (int)mv2, (int)n2, (int)m2);
+            VG_HIP(vg_gemm_launch(&g, st));
+            VGM_LAUNCH1D(vgi_mul_kernel, mv1 * n1, st, P1, P1, mv1 * n1, P1);
+            VGM_LAUNCH1D(vgi_mul_kernel, mv2 * n2, st, P2, P2, mv2 * n2, P2);
+            // Tm[a][j] = sum_i P1^2[a][i] W[j][i];   S[a][b] = sum_j Tm[a][j] P2^2[b][j]
+            if ((rc = gemm1(P1, n1, 1, W, 1, n1, Tm, (int)n2, (int)mv1, (int)n2, (int)n1, st))) return rc;
+            if ((rc = gemm1(Tm, n2, 1, P2, 1, n2, S, (int)mv2, (int)mv1, (int)mv2, (int)n2, st))) return rc;
+        }
+        VGM_LAUNCH1D(vgi_readout_literal_kernel, n_cells, st, S, kd1, kd2, c->theta, dcells, (long)mv2, (long)n_cells, var);
+        VG_HIP(hipGetLastError());
+        VG_HIP(hipStreamSynchronize(st));
+        return VGGP_OK;
+    }
+    const int nbc = (int)std::min<int64_t>(block, n_cells);
+    VgReadout r;
+    if ((rc = vgi_readout_prepare(w, r, nbc, false))) return rc;
+    VgIter& it = r.it;
+    if (!scattered)
+        hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
+    const double p = scattered ? 1.0 / (double)n1 : n_obs / ((double)n1 * (double)n2);
+    const long nb = M * nbc;
+    int max_its = 0, solves = 0;
+    for (int64_t off = 0; off < n_cells; off += nbc) {
+        const int cn = (int)std::min<int64_t>(nbc, n_cells - off);
+        const long long* cl = dcells ? dcells + off : nullptr;
+        VGM_LAUNCH1D(vgi_rank1_grid_kernel, nb, st, U1, U2, cl, (long)off, (int)m1, nbc, (int)m2, (long)mv1, (long)mv2, cn, r.T);
+        int iters = 0, nact = 0;
+        if ((rc = vgi_readout_solve(c, w, r, p, tol, max_iter, &iters, &nact, st))) return rc;
+        ++solves;
+        max_its = std::max(max_its, iters);
+        if (info) { info->rounds1 = max_its; info->sweeps1 = solves; }
+        if (nact > 0) {
+            vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left, block solve %d)", fn, tol, max_iter, nact, solves);
+            return VGGP_ENOCONV;
+        }
+        hipLaunchKernelGGL(vgi_readout_reduce_grid_kernel, dim3(cn), dim3(256), 0, st, r.T, it.X, (int)m1, nbc, (int)m2, c->theta, kd1, kd2, cl,
+                           (long)off, (long)mv2, var + off);
+    }
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+extern "C" int vggp_readout_masked_iter(vggp_ctx* c, const double* W, double n_obs, const double* C1, int64_t mv1, const double* C2, int64_t mv2,
+                                        const double* kd1, const double* kd2, const int64_t* cells, int64_t n_cells, double tol, int max_iter,
+                                        int block, double* mean, double* var, int flags, vggp_info* info, void* stream) {
+    return vgi_gridded_run(c, "vggp_readout_masked_iter", false, W, n_obs, C1, mv1, C2, mv2, kd1, kd2, cells, n_cells, tol, max_iter, block, mean,
+                           var, flags, info, stream);
+}
+extern "C" int vggp_readout_scattered_iter(vggp_ctx* c, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1,
+                                           const double* kd2, const int64_t* cells, int64_t n_cells, double tol, int max_iter, int block,
+                                           double* mean, double* var, int flags, vggp_info* info, void* stream) {
+    return vgi_gridded_run(c, "vggp_readout_scattered_iter", true, nullptr, 0.0, C1, mv1, C2, mv2, kd1, kd2, cells, n_cells, tol, max_iter, block,
+                           mean, var, flags, info, stream);
 }

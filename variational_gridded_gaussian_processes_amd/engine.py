@@ -277,7 +277,8 @@ class Engine:
                                  max_iter: int = 100):
         """The scattered step without any M x M matrix or m_d^2 x N buffer (PCG on the Khatri-Rao operator, Lanczos quadrature,
         control-variate traces, fixed probes; include/vggp.h): any M with m_d <= 256.  -> (elbo, grad[5], info) with
-        info['rounds'][0] = PCG iterations.  Read-outs: qv_scattered_iter, posterior_scattered_iter (means only)."""
+        info['rounds'][0] = PCG iterations.  Read-outs: qv_scattered_iter, posterior_scattered_iter (means only), readout_scattered_iter
+        (the gridded q(v): mean and variance)."""
         if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == self.n1):
             raise TypeError("y must be a contiguous float64 GPU tensor with one value per planned point")
         th = (C.c_double * 5)(*[float(t) for t in theta])
@@ -322,6 +323,57 @@ class Engine:
         out = torch.empty(m1, nb, m2, dtype=torch.float64, device=self.device)
         check(self.lib.vggp_kr_back(self._h, _ptr(L), _ptr(R), _ptr(F), m1, m2, N, nb, _ptr(out), _stream(self.device)))
         return out
+
+    def kr_sqgram(self, P1: torch.Tensor, P2: torch.Tensor) -> torch.Tensor:
+        """Squared Gram kernel of the literal gridded read-out: P1 [mv1, N], P2 [mv2, N] -> out [mv1, mv2] = (P1 o P1)(P2 o P2)^T."""
+        mv1, N = P1.shape
+        mv2 = P2.shape[0]
+        if P2.shape[1] != N:
+            raise ValueError("kr_sqgram: P1 [mv1, N], P2 [mv2, N]")
+        for t in (P1, P2):
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
+                raise TypeError("kr_sqgram operands must be contiguous float64 GPU tensors")
+        out = torch.empty(mv1, mv2, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_kr_sqgram(self._h, _ptr(P1), _ptr(P2), mv1, mv2, N, _ptr(out), _stream(self.device)))
+        return out
+
+    def _readout_iter(self, fn, lead, C1, C2, kd1, kd2, literal, cells, variance, tol, max_iter, block):
+        C1, C2 = C1.to(self.device, torch.float64).contiguous(), C2.to(self.device, torch.float64).contiguous()
+        kd1, kd2 = kd1.to(self.device, torch.float64).contiguous(), kd2.to(self.device, torch.float64).contiguous()
+        if C1.shape[1] != self.m1 or C2.shape[1] != self.m2 or kd1.numel() != C1.shape[0] or kd2.numel() != C2.shape[0]:
+            raise ValueError("C_d must be [mv_d, m_d] and kd_d [mv_d]")
+        mv1, mv2 = C1.shape[0], C2.shape[0]
+        mean = torch.empty(mv1, mv2, dtype=torch.float64, device=self.device)
+        info = Info()
+        if not variance:
+            cp, nc, var = None, 0, None
+        elif cells is None:
+            cp, nc = None, mv1 * mv2
+            var = torch.empty(nc, dtype=torch.float64, device=self.device)
+        else:
+            ca = np.ascontiguousarray(torch.as_tensor(cells).detach().cpu().numpy().reshape(-1), dtype=np.int64)
+            cp, nc = ca.ctypes.data_as(C.POINTER(C.c_int64)), len(ca)
+            var = torch.empty(nc, dtype=torch.float64, device=self.device) if nc else None
+        check(fn(self._h, *lead, _ptr(C1), mv1, _ptr(C2), mv2, _ptr(kd1), _ptr(kd2), cp, nc, float(tol), int(max_iter), int(block),
+                 _ptr(mean), _ptr(var), 1 if literal else 0, C.byref(info), _stream(self.device)))
+        return mean, var, self._info(info)
+
+    def readout_masked_iter(self, C1: torch.Tensor, C2: torch.Tensor, kd1: torch.Tensor, kd2: torch.Tensor, W: torch.Tensor,
+                            n_obs: float, literal: bool = True, cells=None, variance: bool = True, tol: float = 1e-10,
+                            max_iter: int = 100, block: int = 0):
+        """Gridded read-out q(v) after elbo_step_masked_iter (W, n_obs: the step's; C_d, kd_d as readout): -> (mean [mv1, mv2],
+        var [n_cells] or None, info).  cells: flat indices a*mv2 + b (None: every cell); variance=False: the mean only.
+        literal=True: the reference's variance, a Gram product over the data (no solve, info['sweeps'][0] == 0); literal=False: the
+        conditional variance, ceil(n_cells / block) block PCG solves."""
+        self._check_Y(W)
+        return self._readout_iter(self.lib.vggp_readout_masked_iter, (_ptr(W), float(n_obs)), C1, C2, kd1, kd2, literal, cells, variance,
+                                  tol, max_iter, block)
+
+    def readout_scattered_iter(self, C1: torch.Tensor, C2: torch.Tensor, kd1: torch.Tensor, kd2: torch.Tensor, literal: bool = True,
+                               cells=None, variance: bool = True, tol: float = 1e-10, max_iter: int = 100, block: int = 0):
+        """Gridded read-out q(v) after elbo_step_scattered_iter; arguments and result as readout_masked_iter."""
+        return self._readout_iter(self.lib.vggp_readout_scattered_iter, (), C1, C2, kd1, kd2, literal, cells, variance, tol, max_iter,
+                                  block)
 
     def qv_masked(self) -> Tuple[torch.Tensor, torch.Tensor]:
         """-> mean, var [m1, m2]; on a paired plan q(u) over the M inducing points, [M] each."""

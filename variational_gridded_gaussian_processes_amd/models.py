@@ -204,8 +204,9 @@ class KroneckerStructure(torch.nn.Module):
         `solver` does not apply to scattered points or paired inducing points: "iterative" raises ValueError there.
         scattered_solver: how scattered points (along-track data) are solved.  "dense": the M x M solver (M <= 16384, four
         m_d^2 x N buffers); "iterative": PCG on the Khatri-Rao operator without any of them (Engine.elbo_step_scattered_iter; q_v()
-        and posterior() then carry means only); "auto": iterative only when M exceeds the dense solver's limit ("iterative" on a grid
-        with holes, which `solver` governs otherwise, treats it as its observed points).  A model whose
+        and posterior() of the inducing features then carry means only, the gridded q_v() of the Gridded* classes mean and variance);
+        "auto": iterative only when M exceeds the dense solver's limit ("iterative" on a grid with holes, which `solver` governs
+        otherwise, treats it as its observed points).  A model whose
         inducing points are trained (SVGP, train_z=True) keeps the dense path: its Z-gradient reads dense state."""
         super().__init__()
         if solver not in ("auto", "dense", "iterative"):
@@ -279,8 +280,8 @@ class KroneckerStructure(torch.nn.Module):
         return want
 
     def _scattered_iter_variance(self):
-        raise NotImplementedError(f"{type(self).__name__}: the iterative scattered solver provides means only; variances and covariances "
-                                  f"are a block PCG solve with the same operator and are the follow-up to vggp_qv_scattered_iter / "
+        raise NotImplementedError(f"{type(self).__name__}: the iterative scattered solver provides means only here; point-wise variances and "
+                                  f"covariances are block PCG solves with the same operator and are the follow-up to vggp_qv_scattered_iter / "
                                   f"vggp_posterior_scattered_iter (scattered_solver='dense' has them for M <= 16384)")
 
     def _as_scattered(self):
@@ -597,13 +598,36 @@ class Matern12VFFGP(KroneckerStructure):
         return "vff", g1, g2
 
 
-def _no_gridded_readout(model):
-    if model._siter:
-        raise NotImplementedError(f"{type(model).__name__}: the gridded read-out q_v() is not available on the iterative scattered solver "
-                                  f"(q_u() and posterior() means are)")
-    if model._iter:
-        raise NotImplementedError(f"{type(model).__name__}: the gridded read-out q_v() is not available on the iterative masked solver "
-                                  f"(q_u(), q_v_at() on the inducing features and posterior() are)")
+def _gridded_q_v(model, literal: bool, cells=None) -> MultivariateNormal:
+    """q(v) of the B0 cell features on the output grid of a Gridded* model, from the engine state of the current hyper-parameters
+    (flat index a * nsplines + b; `cells`: only those).  Dense solvers: vggp_readout / vggp_readout_masked.  Iterative solvers
+    (solver= / scattered_solver=): vggp_readout_masked_iter / vggp_readout_scattered_iter -- literal=True is a Gram product over the
+    data and comes at once; literal=False costs ceil(cells / 64) block PCG solves, so without `cells` the mean comes now and the
+    variance on first use, and there is no dense covariance."""
+    model._refresh()
+    C1, C2, kd1, kd2 = model._readout_operands()
+    idx = None if cells is None else torch.as_tensor(cells, dtype=torch.int64).reshape(-1)
+    if not (model._siter or model._iter):
+        mean, var = model._engine.readout(C1, C2, kd1, kd2, literal=literal, masked=model._masked)
+        mean, var = mean.reshape(-1).cpu(), var.reshape(-1).cpu()
+        return MultivariateNormal(mean, var) if idx is None else MultivariateNormal(mean[idx], var[idx])
+
+    def run(variance: bool):
+        kw = dict(literal=literal, cells=idx, variance=variance, tol=model.tol, max_iter=model.max_iter)
+        if model._siter:
+            return model._engine.readout_scattered_iter(C1, C2, kd1, kd2, **kw)
+        return model._engine.readout_masked_iter(C1, C2, kd1, kd2, model._W, model._nobs, **kw)
+    if literal or idx is not None:
+        mean, var, model.last_readout_info = run(True)
+        mean = mean.reshape(-1).cpu()
+        return MultivariateNormal(mean if idx is None else mean[idx], var.cpu())
+    mean = run(False)[0]
+
+    def var():
+        model._refresh()                 # the engine may have been re-planned by another model since
+        _, v, model.last_readout_info = run(True)
+        return v.cpu()
+    return MultivariateNormal(mean.reshape(-1).cpu(), var)
 
 
 def _b0_kvv_diag_unit(delta: float, ell: float) -> float:
@@ -641,18 +665,25 @@ class GriddedMatern12VFFGP(Matern12VFFGP):
         """:613-624 -- the posterior over the Fourier features (what the parent class calls q_v)."""
         return super().q_v()
 
-    def q_v(self, psd: bool = True, literal: bool = True) -> MultivariateNormal:
-        """:634-654 (mean and the diagonal of the covariance; flat index a * nsplines + b)."""
-        self._refresh()
-        _no_gridded_readout(self)
+    def _readout_operands(self):
+        """C_d (nsplines x m_d) and the unit diagonals of Kvv_d at the current lengthscales."""
         C1 = self._Kvu_along_dim(self.mesh_1, self.dim1lims[0], self.omegas_1)
         C2 = self._Kvu_along_dim(self.mesh_2, self.dim2lims[0], self.omegas_2)
         l1 = self.kernel_1.base_kernel.lengthscale.reshape(()).item()
         l2 = self.kernel_2.base_kernel.lengthscale.reshape(()).item()
         kd1 = torch.full((self.nsplines,), _b0_kvv_diag_unit(float(self.delta_1.double()), l1), dtype=torch.float64)
         kd2 = torch.full((self.nsplines,), _b0_kvv_diag_unit(float(self.delta_2.double()), l2), dtype=torch.float64)
-        mean, var = self._engine.readout(C1, C2, kd1, kd2, literal=literal, masked=self._masked)
-        return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu())
+        return C1, C2, kd1, kd2
+
+    def q_v(self, psd: bool = True, literal: bool = True) -> MultivariateNormal:
+        """:634-654 (mean and the diagonal of the covariance; flat index a * nsplines + b).  On the iterative solvers see
+        _gridded_q_v: literal=False computes the variance on first use."""
+        return _gridded_q_v(self, literal)
+
+    def q_v_cells(self, cells, literal: bool = False) -> MultivariateNormal:
+        """q_v() at a list of output cells (flat indices a * nsplines + b): on the iterative solvers ceil(len(cells) / 64) block
+        solves for literal=False; elsewhere it indexes q_v().  (q_v_at is the parent's: cells of the inducing features.)"""
+        return _gridded_q_v(self, literal, cells)
 
 
 def _b0_cross_points(mesh: torch.Tensor, z: torch.Tensor, ell: float) -> torch.Tensor:
@@ -686,17 +717,23 @@ class _GriddedReadout:
         """The posterior over the inducing features (what the Kronecker base class calls q_v)."""
         return KroneckerStructure.q_v(self)
 
-    def q_v(self, psd: bool = True, literal: bool = True) -> MultivariateNormal:
-        """mean and the diagonal of the covariance of the B0 cell features (flat index a * nsplines + b); the variance is the
-        reference's own expression (literal=True) unless literal=False asks for the conditional variance under q(u)."""
-        self._refresh()
-        _no_gridded_readout(self)
+    def _readout_operands(self):
         l1 = self.kernel_1.base_kernel.lengthscale.reshape(()).item()
         l2 = self.kernel_2.base_kernel.lengthscale.reshape(()).item()
         kd1 = torch.full((self.nsplines,), _b0_kvv_diag_unit(float(self.b0_delta_1.double()), l1), dtype=torch.float64)
         kd2 = torch.full((self.nsplines,), _b0_kvv_diag_unit(float(self.b0_delta_2.double()), l2), dtype=torch.float64)
-        mean, var = self._engine.readout(self._cross(0, l1), self._cross(1, l2), kd1, kd2, literal=literal, masked=self._masked)
-        return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu())
+        return self._cross(0, l1), self._cross(1, l2), kd1, kd2
+
+    def q_v(self, psd: bool = True, literal: bool = True) -> MultivariateNormal:
+        """mean and the diagonal of the covariance of the B0 cell features (flat index a * nsplines + b); the variance is the
+        reference's own expression (literal=True) unless literal=False asks for the conditional variance under q(u) -- on the
+        iterative solvers that one is computed on first use (see _gridded_q_v)."""
+        return _gridded_q_v(self, literal)
+
+    def q_v_cells(self, cells, literal: bool = False) -> MultivariateNormal:
+        """q_v() at a list of output cells (flat indices a * nsplines + b): on the iterative solvers ceil(len(cells) / 64) block
+        solves for literal=False; elsewhere it indexes q_v().  (q_v_at is the base class's: cells of the inducing features.)"""
+        return _gridded_q_v(self, literal, cells)
 
 
 class Matern12B1SplineASVGP(KroneckerStructure):
@@ -965,6 +1002,8 @@ class GriddedMatern12SVGP(_GriddedReadout, KroneckerStructure):
         if self.inducing == "general":
             return qu
         idx = torch.as_tensor(self._u_of_row)
+        if callable(qu._variance):       # iterative solvers: the variance stays lazy (block solves, or not provided: scattered)
+            return MultivariateNormal(qu.mean[idx], lambda: qu.variance[idx])
         return MultivariateNormal(qu.mean[idx], qu.variance[idx])
 
 
