@@ -171,7 +171,10 @@ int vggp_elbo_step(vggp_ctx* ctx, const double* Y, double yy_total, const double
 
 /* The two halves of the step, for callers that carry the all-reduce themselves (vggp_elbo_step on a multi-rank context
  * does all three): partials fills `payload` (DEVICE, vggp_payload_len doubles) with this rank's contribution; the caller
- * sums it over ranks with ONE all-reduce and passes the reduced buffer to finish. */
+ * sums it over ranks with ONE all-reduce and passes the reduced buffer to finish.  The buffer is the caller's again when finish
+ * returns: after a warm-started step finish keeps its own copy of the reduced payload (one device-to-device copy of
+ * vggp_payload_len doubles on the step's stream, about 10 us), so the read-outs that follow (vggp_qv, vggp_qv_cov, vggp_posterior,
+ * vggp_posterior_cov, vggp_readout) have the accuracy they have after vggp_elbo_step. */
 int vggp_elbo_partials(vggp_ctx* ctx, const double* Y, const double theta[5],
                        double* payload, void* stream);
 int vggp_elbo_finish(vggp_ctx* ctx, const double* payload, double yy_total, const double theta[5],

@@ -387,6 +387,25 @@ def posterior(st: StepState, f1: Factor, f2: Factor, x_star: np.ndarray):
     return mean, var
 
 
+def posterior_cov(st: StepState, f1: Factor, f2: Factor, x_star: np.ndarray) -> np.ndarray:
+    """Dense covariance of posterior(x_star) (N*, N*); kronecker_structure.py:223-229:
+    K** + sum_ij T1[i,p] T1[i,q] (1/D_ij - 1) T2[j,p] T2[j,q], T_d as in posterior(), K** = s1 s2 kappa1 kappa2."""
+    ell1, ell2, s1, s2, v = st.theta
+    x_star = np.asarray(x_star, float)
+    ns = x_star.shape[0]
+    Ts, kap = [], []
+    for f, d, ell, s, col in ((f1, st.d1, ell1, s1, 0), (f2, st.d2, ell2, s2, 1)):
+        xs = x_star[:, col]
+        _, _, A0, _ = f.build(ell, x=xs)
+        Ts.append(d.Q.T @ sla.solve_triangular(d.L, A0 if f.inverse else s * A0, lower=True))
+        kap.append(kappa_and_dell(f.kind, np.abs(xs[:, None] - xs[None, :]), ell)[0])
+    T1, T2 = Ts
+    P1 = (T1[:, :, None] * T1[:, None, :]).reshape(T1.shape[0], ns * ns)      # T1[i,p] T1[i,q]
+    P2 = (T2[:, :, None] * T2[:, None, :]).reshape(T2.shape[0], ns * ns)
+    corr = (P1 * ((1.0 / st.D - 1.0) @ P2)).sum(0).reshape(ns, ns)
+    return s1 * s2 * kap[0] * kap[1] + corr
+
+
 # ----------------------------------------------------------------------------
 # Kron solve  X = K1^{-1} Y K2^{-T}  from Cholesky factors (BASELINE metric ii)
 # ----------------------------------------------------------------------------

@@ -43,6 +43,30 @@ def test_structured_oracle_reproduces_dense_golden(path):
     assert rel(pv, g["post_var"]) < 1e-7
 
 
+@pytest.mark.parametrize("name", ["pts_m12_16x12", "b0_m12_f32mesh_16x12", "vff_m12_24x20"])
+def test_structured_posterior_cov_equals_dense(name):
+    """Kr.posterior_cov (K** + the Kronecker correction in the eigenbasis) == the covariance matrix of the dense restatement's
+    posterior(x*), one golden shape per basis family, at the bound of post_var above (1e-7 of the largest entry); its diagonal
+    is Kr.posterior's variance."""
+    g = np.load(os.path.join(GOLD, f"oracle_{name}.npz"))
+    f1, f2 = factors(g)
+    n1, n2 = len(g["x1"]), len(g["x2"])
+    st = Kr.elbo_step(g["y"].reshape(n2, n1), f1, f2, g["theta"])
+    basis = str(g["basis"])
+    if basis == "vff":
+        g1, g2 = [(float(gr[0]), float(gr[1]), len(gr) - 3) for gr in (g["grid1"], g["grid2"])]
+    else:
+        mesh_dt = torch.float32 if bool(g["mesh_is_f32"]) else torch.float64
+        g1, g2 = torch.tensor(g["grid1"]).to(mesh_dt), torch.tensor(g["grid2"]).to(mesh_dt)
+    dm = D.DenseKron(g["X"], g["y"], basis, str(g["kind"]), g1, g2, raw=g["raw"])
+    ref = dm.posterior(g["xs"]).covariance_matrix.detach().numpy()
+    cov = Kr.posterior_cov(st, f1, f2, g["xs"])
+    assert cov.shape == ref.shape and ref.shape[0] == len(g["xs"]) > 1
+    assert rel(cov, ref) < 1e-7
+    assert np.abs(cov - cov.T).max() <= 1e-12 * np.abs(cov).max()
+    assert rel(np.diag(cov), Kr.posterior(st, f1, f2, g["xs"])[1]) < 1e-12
+
+
 @pytest.mark.parametrize("path", CASES[:3], ids=lambda p: os.path.basename(p)[7:-4])
 def test_dense_oracle_regenerates_golden(path):
     g = np.load(path)

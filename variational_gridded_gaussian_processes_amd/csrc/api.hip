@@ -1693,7 +1693,15 @@ static int elbo_finish_once(vggp_ctx* c, const double* payload, double yy_total,
                             : VG_G_FINISH_COLD, key, st,
                    [&] { return finish_enqueue(c, payload, yy_total, warm, st, true, false, extrap, refine, subspace, false, newton); });
     if (rc) return rc;
-    c->last_warm = warm; c->last_slabs = false; c->last_payload = payload; c->last_yy = yy_total;
+    // The read-outs after a WARM step re-run the finish half cold on the step's reduced G2, H2, C (vg_accurate_state), and the caller's
+    // buffer is the caller's again once this call returns: keep a copy in the context's own payload buffer, which this entry point
+    // leaves unused -- one device-to-device copy on the step's stream, behind the graph.  (A cold step's read-outs rebuild nothing.)
+    const double* kept = payload;
+    if (warm && payload != c->payload) {
+        VG_HIP(hipMemcpyAsync(c->payload, payload, sizeof(double) * c->payload_len, hipMemcpyDeviceToDevice, st));
+        kept = c->payload;
+    }
+    c->last_warm = warm; c->last_slabs = false; c->last_payload = kept; c->last_yy = yy_total;
     return finish_collect(c, elbo_out, grad_out, info, st);
 }
 
@@ -1730,6 +1738,10 @@ static int vg_cold_thin_prepass(vggp_ctx* c, const double* payload, hipStream_t 
 
 static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const double theta[5], double* elbo_out,
                           double grad_out[5], vggp_info* info, void* stream);
+// The early pass over Y whitens afterwards, S = L^-1 (A Y): its rounding grows with cond(Kuu).  Where a factor needed jitter in the
+// last step (RBF points: cond ~ 1e10) the REGULAR warm chains keep the late association (L^-1 A) Y -- with the early one the gradient
+// of a warm step at 192 x 192, m_d = 24 was 3.4e-7 off the oracle.  (The thin chain's own early projection is not affected.)
+static bool vg_jittered(const vggp_ctx* c) { return c->h_out->jitter[0] > 0.0 || c->h_out->jitter[1] > 0.0; }
 // A step whose subspace start turns out to have missed part of the range (VG_ESUBMISS: the hyper-parameters jumped) is repeated
 // once, cold -- the failed attempt has already reset the warm start.  A jump the host can see beforehand (> 5 % in a lengthscale
 // since the last step; the Gram matrices depend on nothing else) skips the attempt.
@@ -1782,7 +1794,7 @@ static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const d
         const bool thin_early = thin && early_ok && !extrap;
         // (the regular warm chains take the early association too, as in the fused single-rank step: the two must agree to rounding)
         static const bool no_early_reg_mr = getenv("VGGP_NO_EARLY_REG") != nullptr;
-        const bool early_mr = thin_early || (warm && !thin && !subspace && early_ok && !no_early_reg_mr);
+        const bool early_mr = thin_early || (warm && !thin && !subspace && early_ok && !no_early_reg_mr && !vg_jittered(c));
         rc = run_graph(c, early_mr ? (extrap ? VG_G_PARTIALS_XE : VG_G_PARTIALS_E) : extrap ? VG_G_PARTIALS_X : VG_G_PARTIALS, kp, st,
                        [&] { return vg_partials_enqueue(c, Y, c->payload, st, true, extrap, false, apply_ns, early_mr ? 1 : 0); }, extrap && !apply_ns);
         {
@@ -1849,7 +1861,7 @@ static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const d
     // used to (beside the refinement kernel) and the main solve carries nothing.  VGGP_NO_EARLY_REG=1: riders as in round 2.
     static const bool no_early_reg = getenv("VGGP_NO_EARLY_REG") != nullptr;
     const bool early_reg = warm && !thin && !subspace && !no_early && !no_early_reg && !no_ride && c->desc.m1 <= 128 && c->desc.m2 <= 128 &&
-                           vg_side(c, st) == st && getenv("VGGP_CHOL_LEGACY") == nullptr && (vg_ride(c) || c->prof);
+                           vg_side(c, st) == st && getenv("VGGP_CHOL_LEGACY") == nullptr && (vg_ride(c) || c->prof) && !vg_jittered(c);
     const int early_mode = thin_early ? 1 : (early_reg ? 2 : 0);
     rc = run_graph(c, warm ? (thin ? VG_G_STEP_WARM_T : newton ? VG_G_STEP_WARM_N : subspace ? VG_G_STEP_WARM_S : extrap ? (refine ? VG_G_STEP_WARM_XR : VG_G_STEP_WARM_X) : VG_G_STEP_WARM)
                             : VG_G_STEP_COLD, key, st, [&] {
@@ -1877,7 +1889,7 @@ static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const d
 static int vg_accurate_state(vggp_ctx* c, hipStream_t st) {
     static const bool skip = getenv("VGGP_FAST_READOUT") != nullptr;
     if ((skip && !c->last_thin) || !c->last_warm || c->acc_valid || !c->have_step) return VGGP_OK;     // (a thin step leaves no m-space state at all)
-    if (c->last_payload != c->payload) return VGGP_OK;       // the caller owned the payload buffer (partials / finish API): not retained
+    if (c->last_payload != c->payload) return VGGP_OK;       // (a caller's payload is not retained; vggp_elbo_finish keeps a copy of a warm step's)
     const long m1 = c->desc.m1, m2 = c->desc.m2;
     if (c->last_slabs) {                                       // fused warm step: G, H, C are still split-K slabs
         VgRedBatch r;
