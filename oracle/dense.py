@@ -262,12 +262,15 @@ class DenseKron:
                    grid_2 are the per-dimension inducing coordinates Z[:, d].
     basis="vff"    Matern12VFFGP (kronecker_structure.py:346-515): grid_d = (a_d, b_d, nfrequencies).
     basis="b1"     Matern12B1SplineASVGP (:524-660): grid_d = knot mesh (nknots).
+    basis and kind may each be a pair (dimension 1, dimension 2): every factor builder, the jitter schedule and the prior term
+    of posterior() read the dimension's own entry (the reference's classes use one family throughout; its algebra is per
+    dimension).  A plain string means the same entry in both dimensions.
     raw: 5 raw parameters [ell1, ell2, s1, s2, noise] (gpytorch init = zeros).
     mask: optional bool (N,) -- observed points; masked-out rows of X, y are dropped
           (the reference simply never sees them).
     """
 
-    def __init__(self, X, y, basis: str, kind: str, grid_1, grid_2, raw=None, mask=None):
+    def __init__(self, X, y, basis, kind, grid_1, grid_2, raw=None, mask=None):
         X = torch.as_tensor(X, dtype=DT)
         y = torch.as_tensor(y, dtype=DT)
         if mask is not None:
@@ -276,17 +279,22 @@ class DenseKron:
         self.train_inputs = (X,)
         self.train_targets = y
         self.basis, self.kind = basis, kind
-        if basis in ("b0", "vff", "b1") and kind != "matern12":
-            raise ValueError("the B0 / VFF / B1 closed forms exist for Matern-1/2 only")
-        if basis == "vff":
-            # grid_d = (a, b, M): domain limits and number of frequencies; omegas as the reference builds them (float32)
-            self.grid_1 = (float(grid_1[0]), float(grid_1[1]), vff_omegas(int(grid_1[2]), float(grid_1[0]), float(grid_1[1])))
-            self.grid_2 = (float(grid_2[0]), float(grid_2[1]), vff_omegas(int(grid_2[2]), float(grid_2[0]), float(grid_2[1])))
-        else:
-            # b0 / b1: keep the mesh dtype as given (float32 in the reference, see b0_Kuu_along_dim)
-            gdt = None if basis in ("b0", "b1") else DT
-            self.grid_1 = torch.as_tensor(grid_1, dtype=gdt)
-            self.grid_2 = torch.as_tensor(grid_2, dtype=gdt)
+        # per-dimension entries: a plain string means the same basis / kernel family in both dimensions
+        self.bases = (basis, basis) if isinstance(basis, str) else tuple(basis)
+        self.kinds = (kind, kind) if isinstance(kind, str) else tuple(kind)
+        if len(self.bases) != 2 or len(self.kinds) != 2:
+            raise ValueError("basis and kind are a string or a pair (dimension 1, dimension 2)")
+        grids = []
+        for b, k, g in zip(self.bases, self.kinds, (grid_1, grid_2)):
+            if b in ("b0", "vff", "b1") and k != "matern12":
+                raise ValueError("the B0 / VFF / B1 closed forms exist for Matern-1/2 only")
+            if b == "vff":
+                # grid_d = (a, b, M): domain limits and number of frequencies; omegas as the reference builds them (float32)
+                grids.append((float(g[0]), float(g[1]), vff_omegas(int(g[2]), float(g[0]), float(g[1]))))
+            else:
+                # b0 / b1: keep the mesh dtype as given (float32 in the reference, see b0_Kuu_along_dim)
+                grids.append(torch.as_tensor(g, dtype=None if b in ("b0", "b1") else DT))
+        self.grid_1, self.grid_2 = grids
         self.raw = (torch.zeros(5, dtype=DT) if raw is None else torch.as_tensor(raw, dtype=DT)).clone()
         self.raw.requires_grad_(True)
         self._jit = None
@@ -302,36 +310,38 @@ class DenseKron:
         # `outputscale` is 0-dim: keep those shapes, they decide torch's type promotion against the float32 mesh
         ell, s = th[d:d + 1], th[2 + d]
         g = self.grid_1 if d == 0 else self.grid_2
-        if self.basis == "b0":
+        basis = self.bases[d]
+        if basis == "b0":
             return b0_Kuu_along_dim(g.shape[0] - 1, g[1] - g[0], ell, s)
-        if self.basis == "vff":
+        if basis == "vff":
             a, b, om = g
             return vff_Kuu_along_dim(a, b, om, ell, s)
-        if self.basis == "b1":
+        if basis == "b1":
             return b1_Kuu_along_dim(g, ell, s)
-        return pairwise(self.kind, g, g, ell, s)
+        return pairwise(self.kinds[d], g, g, ell, s)
 
     def _Kuf_d(self, d: int, x: torch.Tensor) -> torch.Tensor:
         th = self.theta()
         ell, s = th[d:d + 1], th[2 + d]
         g = self.grid_1 if d == 0 else self.grid_2
-        if self.basis == "b0":
+        basis = self.bases[d]
+        if basis == "b0":
             return b0_Kuf_along_dim(g, ell, s, x)
-        if self.basis == "vff":
+        if basis == "vff":
             a, b, om = g
             return vff_Kuf_along_dim(a, b, om, ell, x)
-        if self.basis == "b1":
+        if basis == "b1":
             return b1_Kuf_along_dim(g, x)
-        return pairwise(self.kind, g, x, ell, s)
+        return pairwise(self.kinds[d], g, x, ell, s)
 
     def jitters(self) -> Tuple[float, float]:
         th = self.theta()
-        return tuple(factor_jitter(self._unit(self._Kuu_d(d), th[2 + d])) for d in (0, 1))
+        return tuple(factor_jitter(self._unit(self._Kuu_d(d), th[2 + d], d)) for d in (0, 1))
 
-    def _unit(self, K: torch.Tensor, s) -> torch.Tensor:
-        """The outputscale-free factor the jitter schedule is applied to: K / s, or K * s for the inter-domain bases whose
-        Kuu scales with 1/s (vff, b1)."""
-        return K * s if self.basis in ("vff", "b1") else K / s
+    def _unit(self, K: torch.Tensor, s, d: int) -> torch.Tensor:
+        """The outputscale-free factor of dimension d the jitter schedule is applied to: K / s, or K * s for the inter-domain
+        bases whose Kuu scales with 1/s (vff, b1)."""
+        return K * s if self.bases[d] in ("vff", "b1") else K / s
 
     def _Kuu(self) -> torch.Tensor:
         """:792-806 -- torch.kron(Kuu_1, Kuu_2) (jittered factors, see header)."""
@@ -339,8 +349,8 @@ class DenseKron:
         th = self.theta()
         for d in (0, 1):
             K = self._Kuu_d(d)
-            jit = factor_jitter(self._unit(K, th[2 + d]))
-            scale = 1.0 / th[2 + d] if self.basis in ("vff", "b1") else th[2 + d]
+            jit = factor_jitter(self._unit(K, th[2 + d], d))
+            scale = 1.0 / th[2 + d] if self.bases[d] in ("vff", "b1") else th[2 + d]
             Ks.append(K + (scale * jit) * torch.eye(K.shape[0], dtype=DT))
         return torch.kron(Ks[0], Ks[1])
 
@@ -357,9 +367,10 @@ class DenseKron:
         th = self.theta()
         ell, s = th[d:d + 1], th[2 + d]
         g = self.grid_1 if d == 0 else self.grid_2
-        if self.basis == "points" and self.kind == "matern12":
+        basis = self.bases[d]
+        if basis == "points" and self.kinds[d] == "matern12":
             return b0_Kuf_along_dim(mesh, ell, s, g)
-        if self.basis == "vff":
+        if basis == "vff":
             a, _, om = g
             om = om.to(DT)
             me = mesh.to(DT)
@@ -368,7 +379,7 @@ class DenseKron:
             kc = (torch.sin(om[1:] * (me[1:] - a)[:, None]) - torch.sin(om[1:] * (me[:-1] - a)[:, None])) / om[1:]
             ks = -(torch.cos(om[1:] * (me[1:] - a)[:, None]) - torch.cos(om[1:] * (me[:-1] - a)[:, None])) / om[1:]
             return torch.cat([k0, kc, ks], dim=1)
-        if self.basis == "b1":
+        if basis == "b1":
             # GriddedMatern12ASVGP._Kvu_along_dim (gridded_kronecker_structure.py:831-838), literally: the B1 knots are the B0
             # mesh padded by `padding` knots on either side; row i holds delta at the two knots of cell i (no hyper-parameter)
             K = g.shape[0]
@@ -447,8 +458,8 @@ class DenseKron:
         Kuf_star = self._Kuf(x_star)
         sigma = self._sigma()
         cond_mu = (Kuf_star.T @ inv_matmul(sigma, Kuf) @ y) / noise
-        k1 = pairwise(self.kind, x_star[:, 0], x_star[:, 0], th[0], th[2])
-        k2 = pairwise(self.kind, x_star[:, 1], x_star[:, 1], th[1], th[3])
+        k1 = pairwise(self.kinds[0], x_star[:, 0], x_star[:, 0], th[0], th[2])
+        k2 = pairwise(self.kinds[1], x_star[:, 1], x_star[:, 1], th[1], th[3])
         term1 = k1 * k2
         term2 = Kuf_star.T @ inv_matmul(sigma, Kuf_star)
         term3 = Kuf_star.T @ inv_matmul(Kuu, Kuf_star)

@@ -430,6 +430,7 @@ class MaskedState:
     N: int
     elbo: float = 0.0
     grad: np.ndarray = field(default_factory=lambda: np.zeros(5))
+    Sig: Optional[np.ndarray] = None     # Sigma~ itself (the literal gridded read-out applies it)
 
 
 def _assemble(P1a, P1b, P2a, P2b, W):
@@ -507,7 +508,7 @@ def elbo_step_masked(Y: np.ndarray, W: np.ndarray, f1: Factor, f2: Factor, theta
         quad = 2 * float(a0 @ C1) - quadMk - 2 * rho * Z
         return -0.5 * (ld - (s1 * s2 / v ** 2) * quad) + (s1 * s2 / (2 * v)) * (2 * tr1 - float((Mk * PT.T).sum()))
 
-    st = MaskedState(theta=np.asarray(theta, float), d1=d1, d2=d2, Sinv=Sinv, A0=A0, N=N)
+    st = MaskedState(theta=np.asarray(theta, float), d1=d1, d2=d2, Sinv=Sinv, A0=A0, N=N, Sig=Sig)
     st.elbo = float(elbo)
     st.grad = np.array([ell_grad(1), ell_grad(2), g_s1, g_s2, g_v])
     return st
@@ -698,6 +699,29 @@ def posterior_masked(st: MaskedState, f1: Factor, f2: Factor, x_star: np.ndarray
     return mean, var
 
 
+def q_v_cov_masked(st: MaskedState, f1: Optional[Factor] = None, f2: Optional[Factor] = None) -> np.ndarray:
+    """Dense M x M covariance of q(v) in masked mode, Kuu Sigma^{-1} Kuu (its diagonal is q_v_masked's variance)."""
+    _, _, s1, s2, _ = st.theta
+    e1 = -1 if (f1 is not None and f1.inverse) else 1
+    e2 = -1 if (f2 is not None and f2.inverse) else 1
+    Lk = np.kron(st.d1.L, st.d2.L)
+    return (s1 ** e1) * (s2 ** e2) * (Lk @ st.Sinv @ Lk.T)
+
+
+def posterior_cov_masked(st: MaskedState, f1: Factor, f2: Factor, x_star: np.ndarray) -> np.ndarray:
+    """Dense covariance of posterior_masked(x_star) (N*, N*): s1 s2 (kappa1 kappa2 - T^T T + T^T Sigma~^{-1} T), T as there."""
+    ell1, ell2, s1, s2, v = st.theta
+    x_star = np.asarray(x_star, float)
+    ts, kap = [], []
+    for f, d, ell, col in ((f1, st.d1, ell1, 0), (f2, st.d2, ell2, 1)):
+        xs = x_star[:, col]
+        _, _, A0, _ = f.build(ell, x=xs)
+        ts.append(sla.solve_triangular(d.L, A0, lower=True))
+        kap.append(kappa_and_dell(f.kind, np.abs(xs[:, None] - xs[None, :]), ell)[0])
+    T = np.einsum("ip,jp->ijp", ts[0], ts[1]).reshape(-1, x_star.shape[0])
+    return s1 * s2 * (kap[0] * kap[1] - T.T @ T + T.T @ st.Sinv @ T)
+
+
 # ----------------------------------------------------------------------------
 # gridded read-out q_u -> p(v|u) -> q_v of B0 cell features (gridded_kronecker_structure.py:396-438, :613-654), Kronecker
 # in the per-dimension cross-covariances
@@ -743,6 +767,21 @@ def readout(st: StepState, f1: Factor, f2: Factor, C1, C2, kd1, kd2, literal: bo
     mean = T1.T @ (st.beta / v) @ T2
     var = s1 * s2 * np.outer(kd1, kd2) + (T1 * T1).T @ W @ (T2 * T2)
     return mean, var
+
+
+def readout_masked(st: MaskedState, C1, C2, kd1, kd2, literal: bool = True):
+    """The gridded read-out from the dense M-space state of a masked / scattered step: mean and variance (mv1, mv2).  Everything at
+    unit outputscale: U_d = L0_d^-1 C_d^T, cell (a, b) owns t = U1[:, a] (x) U2[:, b], rho = s1 s2 / sigma^2:
+    mean = rho U1^T A0 U2, var = s1 s2 (kd1_a kd2_b - |t|^2 + t^T X t) with X = Sigma~ (literal reference) or Sigma~^-1 (conditional).
+    The same for every basis: L^-1 Kuv = sqrt(s) L0^-1 C^T whether Kuu carries s (points, b0) or 1 / s (vff, b1)."""
+    _, _, s1, s2, v = st.theta
+    U1 = sla.solve_triangular(st.d1.L, np.asarray(C1, float).T, lower=True)
+    U2 = sla.solve_triangular(st.d2.L, np.asarray(C2, float).T, lower=True)
+    mean = (s1 * s2 / v) * (U1.T @ st.A0 @ U2)
+    T = np.einsum("ia,jb->ijab", U1, U2).reshape(U1.shape[0] * U2.shape[0], -1)
+    XT = (st.Sig if literal else st.Sinv) @ T
+    var = s1 * s2 * (np.outer(kd1, kd2).reshape(-1) - (T * T).sum(0) + (T * XT).sum(0))
+    return mean, var.reshape(mean.shape)
 
 
 # ----------------------------------------------------------------------------
@@ -862,7 +901,7 @@ def elbo_step_scattered(X: np.ndarray, y: np.ndarray, f1: Factor, f2: Factor, th
         quad = 2 * float(a0 @ C1) - quadMk - 2 * rho * Z
         return -0.5 * (ld - (s1 * s2 / v ** 2) * quad) + (s1 * s2 / (2 * v)) * (2 * tr1 - float((Mk * PT.T).sum()))
 
-    st = MaskedState(theta=np.asarray(theta, float), d1=d1, d2=d2, Sinv=Sinv, A0=A0, N=N)
+    st = MaskedState(theta=np.asarray(theta, float), d1=d1, d2=d2, Sinv=Sinv, A0=A0, N=N, Sig=Sig)
     st.elbo = float(elbo)
     st.grad = np.array([ell_grad(1), ell_grad(2), g_s1, g_s2, g_v])
     return st

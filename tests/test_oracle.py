@@ -392,3 +392,179 @@ def test_iterative_masked_step_matches_the_dense_masked_step():
         assert it.iters < 60
     again = Kr.elbo_step_masked_iter(y.reshape(n, n), Wn, f1, f2, theta, nprobe=16, seed=0)
     assert again.elbo == it.elbo and np.array_equal(again.grad, it.grad)
+
+
+# ---- dimensions that differ in kernel family, basis, m and n: the structured oracle against the per-dimension dense restatement ---------
+import mixed_dims_cases as MX
+
+
+def _raw(theta):
+    return D.raw_from_constrained(theta).numpy()
+
+
+def _assert_step_equals_dense(st, dm, theta):
+    e, g = dm.elbo_and_grad()
+    assert abs(st.elbo - e.item()) <= 1e-11 * abs(e.item()), (st.elbo, e.item())
+    assert rel(Kr.grad_raw(st.grad, _raw(theta)), g.numpy()) < 1e-10
+
+
+@pytest.mark.parametrize("order", MX.ORDERS)
+@pytest.mark.parametrize("name", list(MX.FULL))
+def test_mixed_dimensions_full_grid_oracle_equals_dense(name, order):
+    """oracle/kron.py with a different kernel family and basis in each dimension == oracle/dense.py's DenseKron with per-dimension
+    basis / kind (autograd ELBO): ELBO 1e-11, raw gradient 1e-10 (the bounds of test_scattered_oracle_equals_dense_restatement),
+    q(v) 1e-8, posterior 1e-8 / 1e-7, posterior_cov 1e-7 (those of the golden tests above).  Both dimension orders; the second is
+    the transposed twin of the first, so the two ELBOs agree as well.
+
+    The RBF case carries the jitter 1e-8 on one factor (no golden case does).  The dense restatement then solves with a Sigma whose
+    condition number is at least lambda_max(K0) / 1e-8 ~ m / 1e-8 = 1e9, and a backward-stable float64 solve leaves cond * 1.1e-16 ~
+    1e-7 in what it returns: the two means, which are such solves applied to y, get 1e-7 there (measured 1e-8 ... 3e-8 for
+    lengthscales 2 ... 5); the variances and the ELBO keep their bounds."""
+    d1, d2, n, theta0 = MX.FULL[name]
+    a1, a2, x1, x2, Y, X, y, theta = MX.grid_problem(d1, d2, n, theta0, order)
+    f1, f2 = MX.factor(a1, x1), MX.factor(a2, x2)
+    assert f1.m != f2.m and len(x1) != len(x2) and theta[0] != theta[1] and theta[2] != theta[3]
+    st = Kr.elbo_step(Y, f1, f2, theta)
+    dm = MX.dense(X, y, a1, a2, theta)
+    assert (st.d1.jit, st.d2.jit) == dm.jitters()
+    if name.startswith("rbf"):                           # the jitter pair of the GPU test must have two different entries
+        assert sorted((st.d1.jit, st.d2.jit)) == [0.0, 1e-8]
+    _assert_step_equals_dense(st, dm, theta)
+    tol_mean = 1e-7 if max(st.d1.jit, st.d2.jit) > 0 else 1e-8
+    q = dm.q_v()
+    mean, var = Kr.q_v(st)
+    assert rel(mean.reshape(-1), q.mean.detach().numpy()) < tol_mean and rel(var.reshape(-1), q.variance.detach().numpy()) < 1e-8
+    assert rel(Kr.q_v_cov(st), q.covariance_matrix.detach().numpy()) < 1e-8
+    xs = np.random.default_rng(5).uniform(-0.05, 1.05, (9, 2))
+    p = dm.posterior(xs)
+    pm, pv = Kr.posterior(st, f1, f2, xs)
+    assert rel(pm, p.mean.detach().numpy()) < tol_mean and rel(pv, p.variance.detach().numpy()) < 1e-7
+    assert rel(Kr.posterior_cov(st, f1, f2, xs), p.covariance_matrix.detach().numpy()) < 1e-7
+    if order == "ba":
+        t1, t2, y1, y2, Yt, _, _, tht = MX.grid_problem(d1, d2, n, theta0, "ab")
+        twin = Kr.elbo_step(Yt, MX.factor(t1, y1), MX.factor(t2, y2), tht)
+        assert abs(twin.elbo - st.elbo) <= 1e-11 * abs(st.elbo) and rel(st.grad, twin.grad[MX.SWAP]) < 1e-9
+
+
+MIXED_SPARSE = {"m12_vff9-m12_pts8": (MX.vff(4), MX.pts("matern12", 8)), "rbf_pts6-m32_pts5": (MX.pts("rbf", 6), MX.pts("matern32", 5))}
+
+
+@pytest.mark.parametrize("name", list(MIXED_SPARSE))
+def test_mixed_dimensions_masked_and_scattered_oracles_equal_dense(name):
+    """The masked (32 x 28 grid, 30 % missing) and scattered (700 points) structured oracles with mixed dimensions against the
+    per-dimension dense restatement on the observed subset: ELBO 1e-11, raw gradient 1e-10, q(v) and its covariance 1e-8,
+    posterior(x*) 1e-8 / 1e-7 and its covariance 1e-7."""
+    d1, d2 = MIXED_SPARSE[name]
+    theta = np.array([0.3, 0.25, 1.3, 0.7, 0.02])
+    n1, n2 = 32, 28
+    X, y, x1, x2 = D.gen_grid(n1, n2)
+    Wn = (np.random.default_rng(1).uniform(size=(n2, n1)) > 0.3).astype(np.float64)
+    f1, f2 = MX.factor(d1, x1), MX.factor(d2, x2)
+    xs = np.random.default_rng(5).uniform(0, 1, (9, 2))
+    rng = np.random.default_rng(0)
+    Xs = rng.uniform(0, 1, (700, 2))
+    ys = np.sin(5 * Xs[:, 0]) * np.cos(3 * Xs[:, 1]) + 0.1 * rng.standard_normal(700)
+    for st, dm in ((Kr.elbo_step_masked(y.reshape(n2, n1), Wn, f1, f2, theta), MX.dense(X, y, d1, d2, theta, mask=Wn.reshape(-1) > 0)),
+                   (Kr.elbo_step_scattered(Xs, ys, f1, f2, theta), MX.dense(Xs, ys, d1, d2, theta))):
+        _assert_step_equals_dense(st, dm, theta)
+        q = dm.q_v()
+        mean, var = Kr.q_v_masked(st, f1, f2)
+        assert rel(mean.reshape(-1), q.mean.detach().numpy()) < 1e-8 and rel(var.reshape(-1), q.variance.detach().numpy()) < 1e-8
+        p = dm.posterior(xs)
+        pm, pv = Kr.posterior_masked(st, f1, f2, xs)
+        assert rel(pm, p.mean.detach().numpy()) < 1e-8 and rel(pv, p.variance.detach().numpy()) < 1e-7
+        assert rel(Kr.q_v_cov_masked(st, f1, f2), q.covariance_matrix.detach().numpy()) < 1e-8
+        assert rel(Kr.posterior_cov_masked(st, f1, f2, xs), p.covariance_matrix.detach().numpy()) < 1e-7
+
+
+@pytest.mark.parametrize("literal", [True, False], ids=["literal", "conditional"])
+@pytest.mark.parametrize("name", ["vff-pts", "pts-vff", "b1-pts", "pts-b1"])
+def test_mixed_dimensions_gridded_readout_equals_dense(name, literal):
+    """The gridded read-out with an inverse-scaled basis (VFF, B1: Kuu ~ 1 / s) in one dimension and Matern-1/2 points in the other,
+    output meshes of different sizes, against the dense literal formulas at the 1e-10 / 1e-9 of
+    test_gridded_readout_structured_equals_dense."""
+    inv = MX.vff(4) if "vff" in name else MX.b1(15)
+    d1, d2 = (inv, MX.pts("matern12", 8)) if name.endswith("pts") else (MX.pts("matern12", 8), inv)
+    n1, n2 = 32, 28
+    X, y, x1, x2 = D.gen_grid(n1, n2)
+    theta = np.array([0.3, 0.25, 1.3, 0.7, 0.02])
+    f1, f2 = MX.factor(d1, x1), MX.factor(d2, x2)
+    meshes = [np.asarray(d.grid)[2:-2] if d.basis == "b1" else np.linspace(0.1, 0.9, 7) if d.basis == "vff" else np.linspace(0, 1, 6)
+              for d in (d1, d2)]
+    st = Kr.elbo_step(y.reshape(n2, n1), f1, f2, theta)
+    C1, kd1 = Kr.cross_b0(f1, meshes[0], theta[0])
+    C2, kd2 = Kr.cross_b0(f2, meshes[1], theta[1])
+    assert C1.shape[0] != C2.shape[0]
+    q = MX.dense(X, y, d1, d2, theta).q_v_gridded(torch.tensor(meshes[0]), torch.tensor(meshes[1]), literal=literal)
+    m_, v_ = Kr.readout(st, f1, f2, C1, C2, kd1, kd2, literal=literal)
+    assert rel(m_.reshape(-1), q.mean.detach().numpy()) < 1e-10
+    assert rel(v_.reshape(-1), q.variance.detach().numpy()) < 1e-9
+
+
+@pytest.mark.parametrize("literal", [True, False], ids=["literal", "conditional"])
+def test_mixed_dimensions_masked_gridded_readout_equals_dense(literal):
+    """Kr.readout_masked (the gridded read-out from the dense M-space state) for VFF x Matern-1/2 points on a 32 x 28 grid with 30 %
+    missing against the dense literal formulas on the observed subset (1e-10 / 1e-9 as above); on a full mask it equals the
+    Kronecker read-out."""
+    d1, d2 = MX.vff(4), MX.pts("matern12", 8)
+    n1, n2 = 32, 28
+    X, y, x1, x2 = D.gen_grid(n1, n2)
+    theta = np.array([0.3, 0.25, 1.3, 0.7, 0.02])
+    f1, f2 = MX.factor(d1, x1), MX.factor(d2, x2)
+    meshes = np.linspace(0.1, 0.9, 7), np.linspace(0, 1, 6)
+    C1, kd1 = Kr.cross_b0(f1, meshes[0], theta[0])
+    C2, kd2 = Kr.cross_b0(f2, meshes[1], theta[1])
+    Wn = (np.random.default_rng(1).uniform(size=(n2, n1)) > 0.3).astype(np.float64)
+    st = Kr.elbo_step_masked(y.reshape(n2, n1), Wn, f1, f2, theta)
+    q = MX.dense(X, y, d1, d2, theta, mask=Wn.reshape(-1) > 0).q_v_gridded(torch.tensor(meshes[0]), torch.tensor(meshes[1]), literal=literal)
+    m_, v_ = Kr.readout_masked(st, C1, C2, kd1, kd2, literal=literal)
+    assert m_.shape == (6, 5)
+    assert rel(m_.reshape(-1), q.mean.detach().numpy()) < 1e-10
+    assert rel(v_.reshape(-1), q.variance.detach().numpy()) < 1e-9
+    full = Kr.readout_masked(Kr.elbo_step_masked(y.reshape(n2, n1), np.ones((n2, n1)), f1, f2, theta), C1, C2, kd1, kd2, literal=literal)
+    kron = Kr.readout(Kr.elbo_step(y.reshape(n2, n1), f1, f2, theta), f1, f2, C1, C2, kd1, kd2, literal=literal)
+    assert rel(full[0], kron[0]) < 1e-10 and rel(full[1], kron[1]) < 1e-9
+
+
+def _fd_z(elbo_of, z, h=1e-6):
+    fd = np.zeros(len(z))
+    for i in range(len(z)):
+        zp, zm = z.copy(), z.copy()
+        zp[i] += h
+        zm[i] -= h
+        fd[i] = (elbo_of(zp) - elbo_of(zm)) / (2 * h)
+    return fd
+
+
+@pytest.mark.parametrize("name", ["pts-b0", "vff-pts"])
+def test_z_grad_with_exactly_one_points_dimension(name):
+    """z_grad and z_grad_scattered when only ONE dimension has inducing points: central differences of the ELBO for that dimension
+    (2e-6 / 5e-6 as in the two tests above), exact zeros of length m for the other."""
+    if name == "pts-b0":
+        d1, d2, pd = MX.irregular("matern32", 7), MX.b0(9), 0
+    else:
+        d1, d2, pd = MX.vff(4), MX.irregular("matern52", 6), 1
+    theta = np.array([0.21, 0.27, 1.2, 0.9, 0.02])
+    n1, n2 = 40, 33
+    X, y, x1, x2 = D.gen_grid(n1, n2)
+    Y = y.reshape(n2, n1)
+    dims = [d1, d2]
+    z = np.asarray(dims[pd].grid, float)
+
+    def moved(zz):
+        dd = list(dims)
+        dd[pd] = MX.Dim(dims[pd].kind, "points", zz)
+        return dd
+
+    f1, f2 = MX.factor(d1, x1), MX.factor(d2, x2)
+    g = Kr.z_grad(Kr.elbo_step(Y, f1, f2, theta), f1, f2, Y)
+    fd = _fd_z(lambda zz: Kr.elbo_step(Y, MX.factor(moved(zz)[0], x1), MX.factor(moved(zz)[1], x2), theta).elbo, z)
+    assert np.abs(g[pd] - fd).max() <= 2e-6 * np.abs(fd).max()
+    assert g[1 - pd].shape == ((f1, f2)[1 - pd].m,) and not g[1 - pd].any()
+    rng = np.random.default_rng(4)
+    Xs = rng.uniform(0, 1, (300, 2))
+    ys = np.sin(5 * Xs[:, 0]) * np.cos(4 * Xs[:, 1]) + 0.05 * rng.normal(size=300)
+    g = Kr.z_grad_scattered(Kr.elbo_step_scattered(Xs, ys, f1, f2, theta), Xs, ys, f1, f2)
+    fd = _fd_z(lambda zz: Kr.elbo_step_scattered(Xs, ys, MX.factor(moved(zz)[0], x1), MX.factor(moved(zz)[1], x2), theta).elbo, z)
+    assert np.abs(g[pd] - fd).max() <= 5e-6 * np.abs(fd).max()
+    assert g[1 - pd].shape == ((f1, f2)[1 - pd].m,) and not g[1 - pd].any()
