@@ -248,13 +248,31 @@ int vggp_posterior_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, con
 int vggp_elbo_step_scattered_iter(vggp_ctx* ctx, const double* y, double yy, const double theta[5], int n_probes, double tol,
                                   int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream);
 /* Mean read-outs of the iterative scattered step; both need only a0: mean = (s1 s2 / sigma^2) t^T a0.  VGGP_ESTATE unless the LAST
- * finished step on the context was a successful vggp_elbo_step_scattered_iter.  The POINT-WISE VARIANCES of these two are not provided
- * yet: they are block PCG solves with the same operator (the one vggp_readout_scattered_iter below runs for grid cells) and are the
- * follow-up to these entries.
+ * finished step on the context was a successful vggp_elbo_step_scattered_iter.  The POINT-WISE VARIANCES of these two come from the
+ * vggp_*_var_scattered_iter entries below.
  *   vggp_qv_scattered_iter         mean DEVICE [m1][m2] = L0_1 A0 L0_2^T scaled as vggp_qv_masked_iter scales it (e_d = -1 for VFF / B1)
  *   vggp_posterior_scattered_iter  xs1, xs2 DEVICE [n_star]; mean DEVICE [n_star] */
 int vggp_qv_scattered_iter(vggp_ctx* ctx, double* mean, void* stream);
 int vggp_posterior_scattered_iter(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t n_star, double* mean, void* stream);
+/* The same two read-outs WITH their point-wise variances: vggp_qv_masked_iter / vggp_posterior_masked_iter without W, n_obs, on the
+ * Khatri-Rao operator with p = 1 / N.  Every column is rank one, t = u1 (x) u2, and t^T Sigma~^-1 t comes from block PCG solves over
+ * `block` <= 64 columns at a time (the solve vggp_readout_scattered_iter runs: the step's operator, kept preconditioner basis and
+ * per-column stopping rule; no probes, deterministic; a column's numbers do not depend on its neighbours or on `block`).
+ *   q(v)       t = L0_1[i1,:] (x) L0_2[i2,:];  var = s1^e1 s2^e2 t^T Sigma~^-1 t, e_d = -1 for VFF / B1 and 1 otherwise
+ *              cells  HOST int64 [n_cells] flat indices i1*m2 + i2, or NULL with n_cells = M for every cell (ceil(M / block) solves)
+ *              mean   DEVICE [m1][m2], every cell, as vggp_qv_scattered_iter (NULL to skip);  var DEVICE [n_cells] (NULL with
+ *              n_cells = 0: the mean only, no solve)
+ *   posterior  u_d = L0_d^-1 a_d(x*_d);  mean = (s1 s2 / sigma^2) t^T a0,  var = s1 s2 (1 - |t|^2 + t^T Sigma~^-1 t)
+ *              xs1, xs2, mean, var DEVICE [n_star]
+ *   tol <= 0: 1e-10; max_iter <= 0: 100; block <= 0: the largest of 64, 32, ... with N block < 2^31 and M block < 2^31
+ *   info->rounds1 = largest PCG count, info->sweeps1 = number of block solves
+ * VGGP_ESTATE unless the LAST finished step on the context was a successful vggp_elbo_step_scattered_iter; VGGP_ENOCONV when a column
+ * does not converge; VGGP_EINVAL on a grid plan, on paired or multi-rank contexts, for a cell outside [0, M), block > 64, null
+ * arguments.  The workspace is the iterative read-outs' own: a read-out between two steps leaves the second step's bits unchanged. */
+int vggp_qv_var_scattered_iter(vggp_ctx* ctx, const int64_t* cells, int64_t n_cells, double tol, int max_iter, int block, double* mean,
+                               double* var, vggp_info* info, void* stream);
+int vggp_posterior_var_scattered_iter(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t n_star, double tol, int max_iter,
+                                      int block, double* mean, double* var, vggp_info* info, void* stream);
 /* Building blocks of that step, exported for tests: the two kernels on caller-supplied DEVICE arrays.  L [m1][N], R [m2][N] (one
  * column per point), block vectors [m1][nb][m2], fields [nb][N]; 1 <= m_d <= 256, 1 <= nb <= 64.  The context need not be planned.
  *   field  F[c][k]      = sum_a L[a][k] sum_b V[a][c][b] R[b][k]
@@ -263,6 +281,10 @@ int vggp_kr_field(vggp_ctx* ctx, const double* L, const double* R, const double*
                   double* F, void* stream);
 int vggp_kr_back(vggp_ctx* ctx, const double* L, const double* R, const double* F, int64_t m1, int64_t m2, int64_t N, int64_t nb,
                  double* out, void* stream);
+/* The field kernel with two columns per workgroup instead of four (half the registers, several waves per SIMD): arguments and limits
+ * of vggp_kr_field, and the same bits -- a column's accumulators, k order and reductions do not depend on the column group. */
+int vggp_kr_field2(vggp_ctx* ctx, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                   double* F, void* stream);
 /* Gridded read-out q(v) of B0 cell features after an ITERATIVE step: vggp_readout_masked's algebra and scaling (C_d DEVICE [mv_d][m_d],
  * kd_d DEVICE [mv_d], flags = VGGP_READOUT_LITERAL as there) with Sigma~^-1 applied instead of stored, so M = m1 m2 is not limited.
  * U_d = L0_d^-1 C_d^T; cell (a, b) owns t = U1[:, a] (x) U2[:, b]; rho = s1 s2 / sigma^2; P_d = U_d^T B_d (mv_d x n_d).

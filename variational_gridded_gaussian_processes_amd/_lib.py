@@ -66,7 +66,10 @@ SYMBOLS = {
     "vggp_elbo_step_scattered_iter": (_I, [_P, _P, _D, C.POINTER(_D), _I, _D, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(Info), _P]),
     "vggp_qv_scattered_iter": (_I, [_P, _P, _P]),
     "vggp_posterior_scattered_iter": (_I, [_P, _P, _P, _I64, _P, _P]),
+    "vggp_qv_var_scattered_iter": (_I, [_P, C.POINTER(_I64), _I64, _D, _I, _I, _P, _P, C.POINTER(Info), _P]),
+    "vggp_posterior_var_scattered_iter": (_I, [_P, _P, _P, _I64, _D, _I, _I, _P, _P, C.POINTER(Info), _P]),
     "vggp_kr_field": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "vggp_kr_field2": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "vggp_kr_back": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
     "vggp_readout_masked_iter": (_I, [_P, _P, _D, _P, _I64, _P, _I64, _P, _P, C.POINTER(_I64), _I64, _D, _I, _I, _P, _P, _I,
                                       C.POINTER(Info), _P]),

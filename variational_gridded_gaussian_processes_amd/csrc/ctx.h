@@ -172,6 +172,7 @@ int vg_paired_posterior_cov(vggp_ctx* c, const double* xs1, const double* xs2, i
 void vg_masked_new_plan(vggp_ctx* c);
 // the Khatri-Rao operator of the iterative scattered step (kr.hip): L [m1][N], R [m2][N], block vectors [m1][nb][m2], fields [nb][N]
 hipError_t vg_kr_field_launch(const double* L, const double* R, const double* V, int m1, int m2, long N, int nb, double* F, hipStream_t st);
+hipError_t vg_kr_field2_launch(const double* L, const double* R, const double* V, int m1, int m2, long N, int nb, double* F, hipStream_t st);
 size_t vg_kr_back_scratch(int m1, int m2, long N, int nb);      // doubles of split scratch vg_kr_back_launch needs (bounded whatever N)
 hipError_t vg_kr_back_launch(const double* L, const double* R, const double* F, int m1, int m2, long N, int nb, double* out, double* scratch,
                              hipStream_t st);

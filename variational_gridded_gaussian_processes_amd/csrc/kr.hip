@@ -5,7 +5,8 @@
 // Both are fp64-MFMA GEMMs (64 x 64 tiles, 16-deep k-tiles, 2 x 2 waves of 32 x 32, the register-staged pipeline of gemm_body.h)
 // whose large intermediate never leaves the workgroup:
 //   field   the (m1 nb) x N product V R is multiplied by L[a][k] and summed over a in the epilogue of every 64-row tile: a
-//           workgroup owns 64 points and VG_KR_CG columns c and walks ALL rows a, so F is written once and m1 x nb x N never exists
+//           workgroup owns 64 points and VG_KR_CG columns c (2 in the read-outs' instantiation) and walks ALL rows a, so F is written
+//           once and m1 x nb x N never exists
 //   back    the B operand F[c][k] R[b][k] is formed as the fragment is read from LDS; the L and R tiles of a k-tile are staged
 //           once for VG_KR_CG columns.  The reduction over the points is split over workgroups (slabs summed in fixed order by
 //           vg_red_launch): no atomics, bitwise reproducible.
@@ -30,16 +31,19 @@ struct VgKrArgs {
     int tiles_a, tiles_b;
 };
 
-__global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
-    __shared__ double As[VG_KR_CG][VG_KR_T * VG_KR_RS];
+// The body for CG columns per workgroup.  A column's accumulators, k order, epilogue and butterfly do not depend on CG, so every
+// instantiation writes the same bits.
+template <int CG>
+__device__ __forceinline__ void vg_kr_field_body(const VgKrArgs& A) {
+    __shared__ double As[CG][VG_KR_T * VG_KR_RS];
     __shared__ double Bs[VG_KR_BK * VG_KR_KS];
-    __shared__ double red[VG_KR_CG][2][VG_KR_T];
+    __shared__ double red[CG][2][VG_KR_T];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
     const int fi = lane & 15, fk = lane >> 4;
     const int m1 = A.m1, m2 = A.m2, nb = A.nb;
     const long N = A.N, k0 = (long)blockIdx.x * VG_KR_T;
-    const int c0 = blockIdx.y * VG_KR_CG;
-    const int nc = min(VG_KR_CG, nb - c0);
+    const int c0 = blockIdx.y * CG;
+    const int nc = min(CG, nb - c0);
     const int nat = (m1 + VG_KR_T - 1) / VG_KR_T, nbt = (m2 + VG_KR_BK - 1) / VG_KR_BK, nit = nat * nbt;
     // staging map: V tile [64 a][16 b] is b-contiguous, R tile [16 b][64 k] is k-contiguous; 4 elements per thread and operand
     const int va_b = tid & 15, va_i = tid >> 4;            // rows va_i + 16 r
@@ -47,7 +51,7 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
     const long kcol = k0 + rb_j;
     const bool kok = kcol < N;
     const long kcl = kok ? kcol : N - 1;
-    double ra[VG_KR_CG][4], rb[4];
+    double ra[CG][4], rb[4];
     auto load = [&](int it) {
         const int at = it / nbt, bt = it - at * nbt;
         const int gb = bt * VG_KR_BK + va_b;
@@ -59,7 +63,7 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
             const bool ok = bok && ga < m1;
             const int gac = ga < m1 ? ga : m1 - 1;
 #pragma unroll
-            for (int cc = 0; cc < VG_KR_CG; ++cc) {
+            for (int cc = 0; cc < CG; ++cc) {
                 const int c = cc < nc ? c0 + cc : c0;
                 const double v = A.V[((long)gac * nb + c) * m2 + gbc];
                 ra[cc][r] = ok ? v : 0.0;
@@ -70,10 +74,10 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
             rb[r] = (gk < m2 && kok) ? w : 0.0;
         }
     };
-    vg_d4 acc[VG_KR_CG][2][2];
-    double fsum[VG_KR_CG][2];
+    vg_d4 acc[CG][2][2];
+    double fsum[CG][2];
 #pragma unroll
-    for (int cc = 0; cc < VG_KR_CG; ++cc) {
+    for (int cc = 0; cc < CG; ++cc) {
         fsum[cc][0] = fsum[cc][1] = 0.0;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -85,7 +89,7 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
 #pragma unroll
-            for (int cc = 0; cc < VG_KR_CG; ++cc) As[cc][(va_i + 16 * r) * VG_KR_RS + va_b] = ra[cc][r];
+            for (int cc = 0; cc < CG; ++cc) As[cc][(va_i + 16 * r) * VG_KR_RS + va_b] = ra[cc][r];
             Bs[(rb_k + 4 * r) * VG_KR_KS + rb_j] = rb[r];
         }
         __syncthreads();
@@ -96,7 +100,7 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) bv[j] = Bs[(kk + fk) * VG_KR_KS + wc * 32 + j * 16 + fi];
 #pragma unroll
-            for (int cc = 0; cc < VG_KR_CG; ++cc) {
+            for (int cc = 0; cc < CG; ++cc) {
                 if (cc < nc) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
@@ -122,7 +126,7 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
                         const double l = A.L[(long)(a < m1 ? a : m1 - 1) * N + kc];
                         const double lw = a < m1 ? l : 0.0;
 #pragma unroll
-                        for (int cc = 0; cc < VG_KR_CG; ++cc) {
+                        for (int cc = 0; cc < CG; ++cc) {
                             fsum[cc][j] += lw * acc[cc][i][j][r];
                             acc[cc][i][j][r] = 0.0;
                         }
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
     }
     // rows of a 16 x 16 block live in the four lane groups fk: butterfly over them, then the two row-halves of the wave grid
 #pragma unroll
-    for (int cc = 0; cc < VG_KR_CG; ++cc)
+    for (int cc = 0; cc < CG; ++cc)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             double s = fsum[cc][j];
@@ -144,6 +148,12 @@ __global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) {
     if (tid < VG_KR_T && k0 + tid < N)
         for (int cc = 0; cc < nc; ++cc) A.F[(long)(c0 + cc) * N + k0 + tid] = red[cc][0][tid] + red[cc][1][tid];
 }
+
+__global__ __launch_bounds__(256) void vg_kr_field_kernel(const VgKrArgs A) { vg_kr_field_body<VG_KR_CG>(A); }
+// Two columns per workgroup: half the accumulators and staging registers (126 VGPRs, no AGPRs, 29 KB LDS), so several waves share a SIMD
+// and hide each other's LDS round trip where the 4-column instantiation runs one wave per SIMD.  The read-outs' block solves use it
+// (vgi_readout_solve); measured at 2.2 x the 4-column rate at 16 and at 64 columns.
+__global__ __launch_bounds__(256, 2) void vg_kr_field2_kernel(const VgKrArgs A) { vg_kr_field_body<2>(A); }
 
 __global__ __launch_bounds__(256) void vg_kr_back_kernel(const VgKrArgs A) {
     __shared__ double As[VG_KR_T * VG_KR_RS];              // L tile [64 a][16 k]
@@ -243,6 +253,12 @@ hipError_t vg_kr_field_launch(const double* L, const double* R, const double* V,
     VgKrArgs a{};
     a.L = L; a.R = R; a.V = V; a.F = F; a.N = N; a.m1 = m1; a.m2 = m2; a.nb = nb;
     hipLaunchKernelGGL(vg_kr_field_kernel, dim3((unsigned)((N + VG_KR_T - 1) / VG_KR_T), (unsigned)((nb + VG_KR_CG - 1) / VG_KR_CG)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+hipError_t vg_kr_field2_launch(const double* L, const double* R, const double* V, int m1, int m2, long N, int nb, double* F, hipStream_t st) {
+    VgKrArgs a{};
+    a.L = L; a.R = R; a.V = V; a.F = F; a.N = N; a.m1 = m1; a.m2 = m2; a.nb = nb;
+    hipLaunchKernelGGL(vg_kr_field2_kernel, dim3((unsigned)((N + VG_KR_T - 1) / VG_KR_T), (unsigned)((nb + 1) / 2)), dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

@@ -1763,8 +1763,9 @@ static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, d
     hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
     int iters = 0, nact = nbc;
     for (int k = 0; k < max_iter && nact > 0; ++k) {
-        if (w.scattered) {               // the Khatri-Rao operator of the scattered step (n1 points)
-            VG_HIP(vg_kr_field_launch(B1, B2, it.Pd, (int)m1, (int)m2, n1, nbc, it.F0, st));
+        if (w.scattered) {               // the Khatri-Rao operator of the scattered step (n1 points); the field kernel in its two-column
+                                         // instantiation: the same bits at 2.2 x the rate, at 64 columns and at 16
+            VG_HIP(vg_kr_field2_launch(B1, B2, it.Pd, (int)m1, (int)m2, n1, nbc, it.F0, st));
             VG_HIP(vg_kr_back_launch(B1, B2, it.F0, (int)m1, (int)m2, n1, nbc, it.AP, r.krs, st));
         } else {
             if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
@@ -1792,15 +1793,18 @@ static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, d
 }
 
 // mode 0: posterior at (xs1, xs2)[ncols];  mode 1: q(v) variance at cells[ncols] (host; null: every cell) and the mean of all cells
-static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, const double* W, double n_obs, const int64_t* cells, const double* xs1,
-                           const double* xs2, int64_t ncols, double tol, int max_iter, int block, double* mean, double* var, vggp_info* info,
-                           void* stream) {
+// scattered: the read-outs of vggp_elbo_step_scattered_iter (no W, n_obs: the Khatri-Rao operator over the n1 = N points, p = 1 / N)
+static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered, const double* W, double n_obs, const int64_t* cells,
+                           const double* xs1, const double* xs2, int64_t ncols, double tol, int max_iter, int block, double* mean, double* var,
+                           vggp_info* info, void* stream) {
     if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
     VG_NOT_PAIRED(c, fn);
-    VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: the context was planned for scattered points", fn);
+    if (scattered) VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: plan the context with VGGP_FLAG_SCATTERED", fn);
+    else VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: the context was planned for scattered points", fn);
     VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
     const long m1 = c->desc.m1, m2 = c->desc.m2, n1 = c->desc.n1, n2 = c->desc.n2, M = m1 * m2;
-    VG_REQUIRE(W && ncols >= 0 && std::isfinite(n_obs) && n_obs > 0.0, "%s: bad argument", fn);
+    VG_REQUIRE(ncols >= 0, "%s: bad argument", fn);
+    if (!scattered) VG_REQUIRE(W && std::isfinite(n_obs) && n_obs > 0.0, "%s: bad argument", fn);
     VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
     if (mode == 0) VG_REQUIRE(xs1 && xs2 && mean && var, "%s: null argument", fn);
     else {
@@ -1810,10 +1814,15 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, const double* 
             for (int64_t k = 0; k < ncols; ++k)
                 VG_REQUIRE(cells[k] >= 0 && cells[k] < M, "%s: cells[%lld] = %lld is outside [0, M = %ld)", fn, (long long)k, (long long)cells[k], M);
     }
-    auto fits = [&](long b) { return n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31); };
+    auto fits = [&](long b) {
+        return scattered ? (n1 * b < (1L << 31) && M * b < (1L << 31)) : (n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31));
+    };
     if (block <= 0) { block = 64; while (block > 1 && !fits(block)) block >>= 1; }
     VG_REQUIRE(fits(block), "%s: problem too large for block = %d", fn, block);
-    if (!c->have_iter || !c->masked) { vg_set_error("%s: no finished vggp_elbo_step_masked_iter on this context", fn); return VGGP_ESTATE; }
+    if (!c->have_iter || !c->masked) {
+        vg_set_error("%s: no finished %s on this context", fn, scattered ? "vggp_elbo_step_scattered_iter" : "vggp_elbo_step_masked_iter");
+        return VGGP_ESTATE;
+    }
     if (max_iter <= 0) max_iter = 100;
     if (!(tol > 0.0)) tol = 1e-10;
     if (info) { info->jitter1 = info->jitter2 = 0.0; info->sweeps1 = info->sweeps2 = info->rounds1 = info->rounds2 = 0; info->status = 0; info->polished = 0; }
@@ -1835,8 +1844,9 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, const double* 
     VgReadout r;
     if ((rc = vgi_readout_prepare(w, r, nbc, mode == 0))) return rc;
     VgIter& it = r.it;
-    hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
-    const double p = n_obs / ((double)n1 * (double)n2);
+    if (!scattered)
+        hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
+    const double p = scattered ? 1.0 / (double)n1 : n_obs / ((double)n1 * (double)n2);
     const long nb = M * nbc;
     int max_its = 0, solves = 0;
     for (int64_t off = 0; off < ncols; off += nbc) {
@@ -1876,12 +1886,12 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, const double* 
 
 extern "C" int vggp_qv_masked_iter(vggp_ctx* c, const double* W, double n_obs, const int64_t* cells, int64_t n_cells, double tol, int max_iter,
                                    int block, double* mean, double* var, vggp_info* info, void* stream) {
-    return vgi_readout_run(c, "vggp_qv_masked_iter", 1, W, n_obs, cells, nullptr, nullptr, n_cells, tol, max_iter, block, mean, var, info, stream);
+    return vgi_readout_run(c, "vggp_qv_masked_iter", 1, false, W, n_obs, cells, nullptr, nullptr, n_cells, tol, max_iter, block, mean, var, info, stream);
 }
 
 extern "C" int vggp_posterior_masked_iter(vggp_ctx* c, const double* W, double n_obs, const double* xs1, const double* xs2, int64_t ns,
                                           double tol, int max_iter, int block, double* mean, double* var, vggp_info* info, void* stream) {
-    return vgi_readout_run(c, "vggp_posterior_masked_iter", 0, W, n_obs, nullptr, xs1, xs2, ns, tol, max_iter, block, mean, var, info, stream);
+    return vgi_readout_run(c, "vggp_posterior_masked_iter", 0, false, W, n_obs, nullptr, xs1, xs2, ns, tol, max_iter, block, mean, var, info, stream);
 }
 
 // ================================================================================================================================
@@ -2294,6 +2304,19 @@ extern "C" int vggp_posterior_scattered_iter(vggp_ctx* c, const double* xs1, con
     return VGGP_OK;
 }
 
+// q(v) and posterior(x*) WITH their point-wise variances after the iterative scattered step: the iterative masked read-outs
+// (vgi_readout_run) on the Khatri-Rao operator, ceil(columns / block) block PCG solves in the read-outs' own workspace
+extern "C" int vggp_qv_var_scattered_iter(vggp_ctx* c, const int64_t* cells, int64_t n_cells, double tol, int max_iter, int block, double* mean,
+                                          double* var, vggp_info* info, void* stream) {
+    return vgi_readout_run(c, "vggp_qv_var_scattered_iter", 1, true, nullptr, 0.0, cells, nullptr, nullptr, n_cells, tol, max_iter, block, mean,
+                           var, info, stream);
+}
+extern "C" int vggp_posterior_var_scattered_iter(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double tol, int max_iter,
+                                                 int block, double* mean, double* var, vggp_info* info, void* stream) {
+    return vgi_readout_run(c, "vggp_posterior_var_scattered_iter", 0, true, nullptr, 0.0, nullptr, xs1, xs2, ns, tol, max_iter, block, mean, var,
+                           info, stream);
+}
+
 // building blocks, exported for tests: the two kernels of kr.hip on caller-supplied device arrays
 extern "C" int vggp_kr_field(vggp_ctx* c, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
                              double* F, void* stream) {
@@ -2304,6 +2327,19 @@ extern "C" int vggp_kr_field(vggp_ctx* c, const double* L, const double* R, cons
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VG_HIP(vg_kr_field_launch(L, R, V, (int)m1, (int)m2, (long)N, (int)nb, F, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+// the two-column instantiation of the field kernel (bitwise equal to vggp_kr_field; the read-outs' block solves run it)
+extern "C" int vggp_kr_field2(vggp_ctx* c, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                              double* F, void* stream) {
+    if (!c) { vg_set_error("vggp_kr_field2: null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(L && R && V && F, "vggp_kr_field2: null argument");
+    VG_REQUIRE(m1 >= 1 && m1 <= 256 && m2 >= 1 && m2 <= 256 && nb >= 1 && nb <= 64 && N >= 1 && N < (1L << 24),
+               "vggp_kr_field2: need 1 <= m_d <= 256, 1 <= nb <= 64, 1 <= N < 2^24");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VG_HIP(vg_kr_field2_launch(L, R, V, (int)m1, (int)m2, (long)N, (int)nb, F, st));
     VG_HIP(hipStreamSynchronize(st));
     return VGGP_OK;
 }

@@ -277,8 +277,8 @@ class Engine:
                                  max_iter: int = 100):
         """The scattered step without any M x M matrix or m_d^2 x N buffer (PCG on the Khatri-Rao operator, Lanczos quadrature,
         control-variate traces, fixed probes; include/vggp.h): any M with m_d <= 256.  -> (elbo, grad[5], info) with
-        info['rounds'][0] = PCG iterations.  Read-outs: qv_scattered_iter, posterior_scattered_iter (means only), readout_scattered_iter
-        (the gridded q(v): mean and variance)."""
+        info['rounds'][0] = PCG iterations.  Read-outs: qv_scattered_iter, posterior_scattered_iter (means only), their
+        *_var_scattered_iter forms (with point-wise variances), readout_scattered_iter (the gridded q(v): mean and variance)."""
         if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == self.n1):
             raise TypeError("y must be a contiguous float64 GPU tensor with one value per planned point")
         th = (C.c_double * 5)(*[float(t) for t in theta])
@@ -290,7 +290,7 @@ class Engine:
         return elbo.value, np.array(list(grad)), self._info(info)
 
     def qv_scattered_iter(self) -> torch.Tensor:
-        """q(v) mean [m1, m2] after elbo_step_scattered_iter (no solve; the variance is not provided yet)."""
+        """q(v) mean [m1, m2] after elbo_step_scattered_iter (no solve; qv_var_scattered_iter adds the variances)."""
         mean = torch.empty(self.m1, self.m2, dtype=torch.float64, device=self.device)
         check(self.lib.vggp_qv_scattered_iter(self._h, _ptr(mean), _stream(self.device)))
         return mean
@@ -304,14 +304,48 @@ class Engine:
         check(self.lib.vggp_posterior_scattered_iter(self._h, _ptr(xs1), _ptr(xs2), ns, _ptr(mean), _stream(self.device)))
         return mean
 
-    def kr_field(self, L: torch.Tensor, R: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
-        """Khatri-Rao field kernel: L [m1, N], R [m2, N], V [m1, nb, m2] -> F [nb, N], F[c, k] = l_k^T V_c r_k."""
+    def qv_var_scattered_iter(self, cells=None, variance: bool = True, tol: float = 1e-10, max_iter: int = 100, block: int = 0):
+        """q(v) after elbo_step_scattered_iter: -> (mean [m1, m2], var [n_cells] or None, info).  cells, variance, info as
+        qv_masked_iter: None means every cell (ceil(M / block) block PCG solves), variance=False the mean only (no solve)."""
+        mean = torch.empty(self.m1, self.m2, dtype=torch.float64, device=self.device)
+        info = Info()
+        if not variance:
+            cp, nc, var = None, 0, None
+        elif cells is None:
+            cp, nc = None, self.m1 * self.m2
+            var = torch.empty(nc, dtype=torch.float64, device=self.device)
+        else:
+            ca = np.ascontiguousarray(torch.as_tensor(cells).detach().cpu().numpy().reshape(-1), dtype=np.int64)
+            cp, nc = ca.ctypes.data_as(C.POINTER(C.c_int64)), len(ca)
+            var = torch.empty(nc, dtype=torch.float64, device=self.device) if nc else None
+        check(self.lib.vggp_qv_var_scattered_iter(self._h, cp, nc, float(tol), int(max_iter), int(block), _ptr(mean), _ptr(var),
+                                                  C.byref(info), _stream(self.device)))
+        return mean, var, self._info(info)
+
+    def posterior_var_scattered_iter(self, x_star: torch.Tensor, tol: float = 1e-10, max_iter: int = 100, block: int = 0):
+        """posterior(x*) after elbo_step_scattered_iter; x_star [ns, 2] -> (mean [ns], var [ns], info): ceil(ns / block) solves."""
+        xs = x_star.to(self.device, torch.float64)
+        xs1, xs2 = xs[:, 0].contiguous(), xs[:, 1].contiguous()
+        ns = xs1.shape[0]
+        mean = torch.empty(ns, dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mean)
+        info = Info()
+        check(self.lib.vggp_posterior_var_scattered_iter(self._h, _ptr(xs1), _ptr(xs2), ns, float(tol), int(max_iter), int(block),
+                                                         _ptr(mean), _ptr(var), C.byref(info), _stream(self.device)))
+        return mean, var, self._info(info)
+
+    def kr_field(self, L: torch.Tensor, R: torch.Tensor, V: torch.Tensor, cols_per_wg: int = 4) -> torch.Tensor:
+        """Khatri-Rao field kernel: L [m1, N], R [m2, N], V [m1, nb, m2] -> F [nb, N], F[c, k] = l_k^T V_c r_k.  cols_per_wg: 4 (the
+        step's kernel) or 2 (the read-outs' instantiation; the same bits)."""
         m1, N = L.shape
         m2, nb = R.shape[0], V.shape[1]
         if R.shape[1] != N or tuple(V.shape) != (m1, nb, m2):
             raise ValueError("kr_field: L [m1, N], R [m2, N], V [m1, nb, m2]")
+        if cols_per_wg not in (2, 4):
+            raise ValueError("kr_field: cols_per_wg is 2 or 4")
+        fn = self.lib.vggp_kr_field2 if cols_per_wg == 2 else self.lib.vggp_kr_field
         F = torch.empty(nb, N, dtype=torch.float64, device=self.device)
-        check(self.lib.vggp_kr_field(self._h, _ptr(L), _ptr(R), _ptr(V), m1, m2, N, nb, _ptr(F), _stream(self.device)))
+        check(fn(self._h, _ptr(L), _ptr(R), _ptr(V), m1, m2, N, nb, _ptr(F), _stream(self.device)))
         return F
 
     def kr_back(self, L: torch.Tensor, R: torch.Tensor, F: torch.Tensor) -> torch.Tensor:

@@ -197,17 +197,22 @@ class KroneckerStructure(torch.nn.Module):
     kind = "matern12"
 
     def __init__(self, X: torch.Tensor, y: torch.Tensor, engine: Optional[Engine] = None, warm_start: bool = True,
-                 solver: str = "auto", scattered_solver: str = "auto"):
+                 solver: str = "auto", scattered_solver: str = "auto", scattered_variances: bool = False):
         """solver: how a grid with holes is solved.  "dense": the M x M solver (M = m1 m2 <= 16384); "iterative": PCG without any
         M x M matrix (Engine.elbo_step_masked_iter and its read-outs; also accepted on a full grid, which it treats as a mask of
         ones); "auto": iterative only for a grid with holes whose M exceeds the dense solver's limit, dense everywhere else.
         `solver` does not apply to scattered points or paired inducing points: "iterative" raises ValueError there.
         scattered_solver: how scattered points (along-track data) are solved.  "dense": the M x M solver (M <= 16384, four
         m_d^2 x N buffers); "iterative": PCG on the Khatri-Rao operator without any of them (Engine.elbo_step_scattered_iter; q_v()
-        and posterior() of the inducing features then carry means only, the gridded q_v() of the Gridded* classes mean and variance);
+        and posterior() of the inducing features then carry means only unless scattered_variances is set, the gridded q_v() of the
+        Gridded* classes mean and variance);
         "auto": iterative only when M exceeds the dense solver's limit ("iterative" on a grid with holes, which `solver` governs
         otherwise, treats it as its observed points).  A model whose
-        inducing points are trained (SVGP, train_z=True) keeps the dense path: its Z-gradient reads dense state."""
+        inducing points are trained (SVGP, train_z=True) keeps the dense path: its Z-gradient reads dense state.
+        scattered_variances: on the iterative scattered solver, give q_v(), q_u(), posterior() and posterior_predictive() their
+        point-wise variances (Engine.qv_var_scattered_iter / posterior_var_scattered_iter: ceil(columns / 64) block PCG solves; the
+        all-cell variance of q_v() is computed on first use).  False keeps the means-only distributions, whose .variance raises;
+        q_v_at(cells) gives the variance of a few cells either way.  No effect on the other solvers."""
         super().__init__()
         if solver not in ("auto", "dense", "iterative"):
             raise ValueError(f"solver must be 'auto', 'dense' or 'iterative', got {solver!r}")
@@ -215,6 +220,8 @@ class KroneckerStructure(torch.nn.Module):
             raise ValueError(f"scattered_solver must be 'auto', 'dense' or 'iterative', got {scattered_solver!r}")
         self.solver = solver
         self.scattered_solver = scattered_solver
+        self.scattered_variances = bool(scattered_variances)
+        self.last_readout_info = None    # PCG counts of the last variance read-out on an iterative solver
         self._siter = False              # the iterative scattered step applies (decided at plan time)
         self.n_probes, self.tol, self.max_iter = 16, 1e-10, 100      # of the iterative solver (the engine's defaults)
         self._iter = False
@@ -280,9 +287,10 @@ class KroneckerStructure(torch.nn.Module):
         return want
 
     def _scattered_iter_variance(self):
-        raise NotImplementedError(f"{type(self).__name__}: the iterative scattered solver provides means only here; point-wise variances and "
-                                  f"covariances are block PCG solves with the same operator and are the follow-up to vggp_qv_scattered_iter / "
-                                  f"vggp_posterior_scattered_iter (scattered_solver='dense' has them for M <= 16384)")
+        raise NotImplementedError(f"{type(self).__name__}: the iterative scattered solver provides means only unless the model is built "
+                                  f"with scattered_variances=True (block PCG solves, the follow-up to vggp_qv_scattered_iter / "
+                                  f"vggp_posterior_scattered_iter; q_v_at(cells) gives a few variances without it); dense covariances "
+                                  f"need scattered_solver='dense' (M <= 16384)")
 
     def _as_scattered(self):
         """Switch a masked-grid model to the scattered representation of the same observations (one coordinate pair per point):
@@ -383,6 +391,12 @@ class KroneckerStructure(torch.nn.Module):
         """gridded_kronecker_structure.py:1409-1433 == kronecker_structure.py:825-849.
         mean is flat (M,) with u = i1*m2 + i2 (callers do `.mean.reshape(m, m).T`)."""
         self._refresh()
+        if self._siter and self.scattered_variances:          # the mean now, the variance of all M cells on first use (as below)
+            def svar():
+                self._refresh()          # the engine may have been re-planned by another model since
+                _, v, self.last_readout_info = self._engine.qv_var_scattered_iter(tol=self.tol, max_iter=self.max_iter)
+                return v.cpu()
+            return MultivariateNormal(self._engine.qv_scattered_iter().reshape(-1).cpu(), svar)
         if self._siter:                  # iterative scattered solver: the mean only (no solve)
             return MultivariateNormal(self._engine.qv_scattered_iter().reshape(-1).cpu(), self._scattered_iter_variance,
                                       cov_fn=self._scattered_iter_variance)
@@ -408,11 +422,14 @@ class KroneckerStructure(torch.nn.Module):
         ceil(len(cells) / 64) block solves instead of the ceil(M / 64) of q_v().variance; elsewhere it indexes q_v()."""
         idx = torch.as_tensor(cells, dtype=torch.int64).reshape(-1)
         self._plan()
-        if not self._iter:
+        if not (self._iter or self._siter):
             qv = self.q_v()
             return MultivariateNormal(qv.mean[idx], qv.variance[idx])
         self._refresh()
-        mean, var, _ = self._engine.qv_masked_iter(self._W, self._nobs, cells=idx, tol=self.tol, max_iter=self.max_iter)
+        if self._siter:                  # (an explicit request: whatever scattered_variances says)
+            mean, var, self.last_readout_info = self._engine.qv_var_scattered_iter(cells=idx, tol=self.tol, max_iter=self.max_iter)
+        else:
+            mean, var, _ = self._engine.qv_masked_iter(self._W, self._nobs, cells=idx, tol=self.tol, max_iter=self.max_iter)
         return MultivariateNormal(mean.reshape(-1).cpu()[idx], var.cpu())
 
     def posterior(self, x_star: torch.Tensor) -> MultivariateNormal:
@@ -420,6 +437,9 @@ class KroneckerStructure(torch.nn.Module):
         N* x N* matrix, :223-229) is materialised on first access (vggp_posterior_cov: N* <= 8192, M N* <= 2^27)."""
         self._refresh()
         xs = torch.as_tensor(x_star, dtype=torch.float64)
+        if self._siter and self.scattered_variances:          # (no dense covariance, as on the iterative masked solver)
+            mean, var, self.last_readout_info = self._engine.posterior_var_scattered_iter(xs, tol=self.tol, max_iter=self.max_iter)
+            return MultivariateNormal(mean.cpu(), var.cpu())
         if self._siter:
             return MultivariateNormal(self._engine.posterior_scattered_iter(xs).cpu(), self._scattered_iter_variance,
                                       cov_fn=self._scattered_iter_variance)
