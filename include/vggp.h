@@ -387,6 +387,42 @@ int vggp_posterior_cov_masked(vggp_ctx* ctx, const double* xs1, const double* xs
 /* Dense M x M covariance of q(v) of the last masked step (Kuu Sigma^-1 Kuu on the observed subset). */
 int vggp_qv_cov_masked(vggp_ctx* ctx, double* cov, void* stream);
 
+/* Exact GP on N scattered points, 1 <= N <= 16384 -- the dense baseline of the reference's notebooks: Matern12GP / Matern32GP /
+ * Matern52GP (src/models/exact/bivariate_structure.py) and GriddedMatern12ExactGP (gridded_kronecker_structure.py:21-211).
+ * kernel = kernel_1 * kernel_2 on active dims 0 and 1, s = s1 s2:
+ *     K0[i, j] = k1(|x_i1 - x_j1| / ell1) k2(|x_i2 - x_j2| / ell2),  Sigma = s K0 + sigma2 I (+ eps I),  alpha = Sigma^-1 y,
+ *     MLL = -1/2 [y^T alpha + log|Sigma| + N log 2 pi]   (what ExactMarginalLogLikelihood returns, times N).
+ * eps follows the psd_safe_cholesky schedule on Sigma itself (0, 1e-8, 1e-7, 1e-6, then VGGP_ENOTPD), reported in vggp_info.jitter1.
+ * The exact state is a workspace of its own on the context (about 4 N^2 doubles, allocated by vggp_exact_plan; VGGP_ENOMEM when the
+ * device cannot hold it): it is independent of vggp_plan -- a planned sparse model keeps its state across exact calls and the exact
+ * state survives a later vggp_plan -- and is replaced by the next vggp_exact_plan.  Single-rank contexts only.
+ *
+ * vggp_exact_plan: x1, x2 HOST [N] coordinates (finite), kind_d one of VGGP_KIND_*. */
+int vggp_exact_plan(vggp_ctx* ctx, int kind1, int kind2, const double* x1, const double* x2, int64_t N);
+/* MLL and its gradient with respect to the constrained theta (as vggp_elbo_step); y DEVICE [N].  Sigma is built from the coordinates,
+ * factored by the blocked MFMA Cholesky + inverse, and W = alpha alpha^T - Sigma^-1 is contracted against K0 and dK0/d ell_d in one pass
+ * over the upper tiles of Sigma^-1 (kernel derivatives evaluated on chip; fixed-order sums: bitwise repeatable).  One host
+ * synchronisation.  Under vggp_profile the step charges the Sigma build to stage 0, Cholesky + inverse to stage 1, alpha to stage 5
+ * and the gradient pass to stage 18. */
+int vggp_exact_step(vggp_ctx* ctx, const double* y, const double theta[5], double* mll_out, double grad_out[5], vggp_info* info,
+                    void* stream);
+/* posterior(x*) of the last exact step at ns test points (DEVICE inputs and outputs): mean = s B*^T alpha,
+ * var = s - s^2 diag(B*^T Sigma^-1 B*), B*[i, p] = k1(x_i1, x*_p1) k2(x_i2, x*_p2) (gpytorch's ExactGP prediction without
+ * fast_pred_var); the predictive distribution adds sigma2.  vggp_exact_posterior_cov: the dense [ns][ns] covariance, ns <= 8192. */
+int vggp_exact_posterior(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var, void* stream);
+int vggp_exact_posterior_cov(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t ns, double* cov, void* stream);
+/* Gridded read-out q(v) of B0 cell features from the last exact step (GriddedMatern12ExactGP.q_v, gridded_kronecker_structure.py
+ * :177-191; Matern-1/2 plans only: the cell integrals are Matern-1/2 closed forms).  C_d DEVICE [mv_d][N] = Cov(v, f(x_i)) along d at
+ * unit outputscale (:52-101), kd_d DEVICE [mv_d] = diag(Kvv_d) / s_d; Kvx[(a, b), i] = s C1[a][i] C2[b][i], cells flat a mv2 + b.
+ * mean, var DEVICE [mv1][mv2]: mean = Kvx alpha; var = s kd1 kd2 + diag(Kvx Kxv) / sigma2 with VGGP_READOUT_LITERAL -- the reference's
+ * Kvv - Kvx Kxx^-1 Kxv + Kvx P^-1 Kxv, P = Kxx - Kxx Sigma^-1 Kxx, in the form P^-1 = Kxx^-1 + I / sigma2 that never inverts Kxx (a
+ * Gram product over the points, no solve) -- and the conditional variance s kd1 kd2 - diag(Kvx Sigma^-1 Kxv) otherwise. */
+int vggp_exact_readout(vggp_ctx* ctx, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1, const double* kd2,
+                       double* mean, double* var, int flags, void* stream);
+/* Errors of the exact entries: VGGP_EINVAL for a null context, N outside [1, 16384], a bad kind, non-finite coordinates, a theta
+ * component <= 0, an n_ranks > 1 context, ns > 8192 (covariance), a read-out of cells on a plan that is not Matern-1/2; VGGP_ESTATE for a
+ * step without a plan or a read-out before a successful step on the current plan. */
+
 /* building blocks (exported for tests, benchmarks and re-use) ---------------- */
 /* Unit-outputscale factor build for one dimension: A0[m][n], dA0/d ell [m][n],
  * K0[m][m], dK0/d ell [m][m] (any output pointer may be NULL).  x DEVICE [n];

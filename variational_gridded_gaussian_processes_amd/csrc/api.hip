@@ -135,6 +135,7 @@ extern "C" int vggp_destroy(vggp_ctx* c) {
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     vg_masked_free(c);
     vg_paired_free(c);
+    vg_exact_free(c);
     vg_comm_destroy(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->arena) (void)hipFree(c->arena);

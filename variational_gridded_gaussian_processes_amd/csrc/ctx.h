@@ -132,6 +132,7 @@ struct vggp_ctx {
     int nev = 0;
     double prof_ms[VGGP_NSTAGE] = {};
     int prof_steps = 0;
+    void* exact = nullptr;           // VgExact workspace (exact.hip): allocated by vggp_exact_plan, independent of vggp_plan's state
 };
 
 
@@ -161,6 +162,7 @@ int vg_paired_readout(vggp_ctx* c, const double* C1, int64_t mv1, const double* 
                       double* mean, double* var, int flags, hipStream_t st);
 int vg_paired_posterior(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var, hipStream_t st);
 int vg_paired_posterior_cov(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* cov, hipStream_t st);
+void vg_exact_free(vggp_ctx* c);      // exact GP (exact.hip)
 // entries that have no paired meaning: VGGP_EINVAL with a message
 #define VG_NOT_PAIRED(c, fn)                                                                                            \
     do {                                                                                                                \

@@ -82,6 +82,8 @@ class Engine:
         self._step_bufs = None
         self.paired = False          # the current plan is a paired one (plan_paired)
         self.plan_token = 0          # bumped by every plan(): a model sharing this engine re-plans when it is not the last planner
+        self.exact_n = 0             # points of the current exact plan (exact_plan)
+        self.exact_token = 0         # ... and its counter, for the exact models that share this engine
 
     @staticmethod
     def unique_id() -> bytes:
@@ -519,6 +521,55 @@ class Engine:
         mean = torch.empty(ns, dtype=torch.float64, device=self.device)
         var = torch.empty_like(mean)
         check(getattr(self.lib, _fn)(self._h, _ptr(xs1), _ptr(xs2), ns, _ptr(mean), _ptr(var), _stream(self.device)))
+        return mean, var
+
+    # -- exact GP (dense N x N, N <= 16384; a workspace of its own beside the planned model) --------------
+    def exact_plan(self, kind1: str, kind2: str, x1, x2) -> None:
+        """Exact GP on the N points (x1[k], x2[k]) with kernel_1 * kernel_2 of the given kinds (vggp_exact_plan).  Independent of
+        plan() / plan_paired(): neither disturbs the other's state."""
+        x1, x2 = _dvec(x1), _dvec(x2)
+        if len(x1) != len(x2):
+            raise ValueError("exact plan: x1 and x2 must hold one coordinate pair per point")
+        with torch.cuda.device(self.device):
+            check(self.lib.vggp_exact_plan(self._h, KIND[kind1], KIND[kind2], x1.ctypes.data, x2.ctypes.data, len(x1)))
+        self.exact_n = len(x1)
+        self.exact_token += 1
+
+    def exact_step(self, y: torch.Tensor, theta: Sequence[float]):
+        """-> (marginal log likelihood, grad[5] wrt (ell1, ell2, s1, s2, sigma2), info dict); y [N] float64 GPU tensor."""
+        if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == self.exact_n):
+            raise TypeError("y must be a contiguous float64 GPU tensor with one value per planned point")
+        th = (C.c_double * 5)(*[float(t) for t in theta])
+        mll = C.c_double()
+        grad = (C.c_double * 5)()
+        info = Info()
+        check(self.lib.vggp_exact_step(self._h, _ptr(y), th, C.byref(mll), grad, C.byref(info), _stream(self.device)))
+        return mll.value, np.array(list(grad)), self._info(info)
+
+    def exact_posterior(self, x_star: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """posterior(x*) of the last exact step; x_star [ns, 2] -> mean[ns], var[ns]."""
+        return self.posterior(x_star, _fn="vggp_exact_posterior")
+
+    def exact_posterior_cov(self, x_star: torch.Tensor) -> torch.Tensor:
+        """Dense covariance of the exact posterior(x*), x_star [ns, 2] (ns <= 8192) -> [ns, ns]."""
+        xs = x_star.to(self.device, torch.float64)
+        xs1, xs2 = xs[:, 0].contiguous(), xs[:, 1].contiguous()
+        ns = xs1.shape[0]
+        cov = torch.empty(ns, ns, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_exact_posterior_cov(self._h, _ptr(xs1), _ptr(xs2), ns, _ptr(cov), _stream(self.device)))
+        return cov
+
+    def exact_readout(self, C1: torch.Tensor, C2: torch.Tensor, kd1: torch.Tensor, kd2: torch.Tensor, literal: bool = True):
+        """Gridded read-out q(v) of B0 cell features from the last exact step (Matern-1/2 plans): C_d [mv_d, N] unit-outputscale
+        Cov(v, f(x_i)) along d, kd_d [mv_d] unit diagonals of Kvv_d -> mean, var [mv1, mv2]."""
+        C1, C2 = C1.to(self.device, torch.float64).contiguous(), C2.to(self.device, torch.float64).contiguous()
+        kd1, kd2 = kd1.to(self.device, torch.float64).contiguous(), kd2.to(self.device, torch.float64).contiguous()
+        if C1.shape[1] != self.exact_n or C2.shape[1] != self.exact_n or kd1.numel() != C1.shape[0] or kd2.numel() != C2.shape[0]:
+            raise ValueError("C_d must be [mv_d, N] and kd_d [mv_d]")
+        mean = torch.empty(C1.shape[0], C2.shape[0], dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mean)
+        check(self.lib.vggp_exact_readout(self._h, _ptr(C1), C1.shape[0], _ptr(C2), C2.shape[0], _ptr(kd1), _ptr(kd2), _ptr(mean),
+                                          _ptr(var), 1 if literal else 0, _stream(self.device)))
         return mean, var
 
     # -- building blocks ------------------------------------------------------------------------------
