@@ -834,9 +834,10 @@ def test_error_paths_of_the_masked_and_scattered_entries(engine):
 
 # ---- iterative masked step: PCG + Lanczos quadrature + control-variate traces, no M x M matrix ----------
 def test_iterative_masked_step_vs_dense_small(engine):
-    """vggp_elbo_step_masked_iter against the dense masked oracle and against its own numpy specification (different probes:
-    same tolerances), B0 / Matern-1/2 and points / Matern-3/2, Bernoulli and track-shaped masks.  Stated tolerances: ELBO 1e-5,
-    gradient 1e-4 of its largest component.  Deterministic: the same sequence of calls gives the same bits."""
+    """vggp_elbo_step_masked_iter against the dense masked oracle (the estimator's noise: the comparison with its own numpy
+    specification on the same probes, at round-off level, is tests/test_gpu_masked_iter_spec.py), B0 / Matern-1/2 and
+    points / Matern-3/2, Bernoulli and track-shaped masks.  Stated tolerances: ELBO 1e-5, gradient 1e-4 of its largest component.
+    Deterministic: the same sequence of calls gives the same bits."""
     from variational_gridded_gaussian_processes_amd import datagen as G
     n = 96
     X, y, x1, x2 = D.gen_grid(n, n)

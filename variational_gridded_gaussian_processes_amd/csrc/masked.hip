@@ -1065,6 +1065,7 @@ struct VgIter {
     double *dg1, *dg2, *Tq;                       // diag(Q^T Mk Q), m x m temporary
     double *Qk1, *Qk2;                            // the preconditioner's eigenbasis of the last cold solve (rows = eigenvectors), kept across steps
     double *ts;                                   // [32] scalars
+    double *fpart;                                // [1024] block partials of the field sums (masked step)
     int* nact;                                    // device word: number of active columns
     int* h_nact;                                  // pinned
 };
@@ -1328,6 +1329,7 @@ static int vgi_prepare(vggp_ctx* c, VgMasked& w, VgIter& it, int nbc, int maxit)
         it.Qk1 = take(m1 * m1); it.Qk2 = take(m2 * m2);
         it.ts = take(64);
         it.nact = reinterpret_cast<int*>(take(8));
+        it.fpart = take(1024);                    // (its own: a block vector has M nbc doubles, which may be fewer than the 1024 partials)
         if (pass == 0) {
             const size_t need = off + 4096;
             if (w.ibytes < need || w.ib_nbc != nbc || w.ib_maxit != maxit) w.ib_valid = false;      // (the layout moves: the kept basis is gone)
@@ -1520,8 +1522,8 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     double* dU = it.Zp;
     // stochastic parts of the traces: fields of dU and of Wz with (B1,B2), (V1,B2), (B1,V2)
     auto fsum = [&](const double* Fa, const double* Fb, double* out) {
-        hipLaunchKernelGGL(vgi_fieldsum_part_kernel, dim3(1024), dim3(256), 0, st, Fa, Fb, it.Wt, n1, nbc, n2, it.AP);      // (AP is free after the PCG)
-        hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.AP, 1024, out, 0);
+        hipLaunchKernelGGL(vgi_fieldsum_part_kernel, dim3(1024), dim3(256), 0, st, Fa, Fb, it.Wt, n1, nbc, n2, it.fpart);
+        hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.fpart, 1024, out, 0);
     };
     if ((rc = vgi_field(w, it, B1, it.Wz, B2, it.F0, st))) return rc;              // F0 = Fw^BB
     if ((rc = vgi_field(w, it, B1, dU, B2, it.F1, st))) return rc;                 // F1 = Fu^BB
