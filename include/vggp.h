@@ -423,7 +423,66 @@ int vggp_exact_readout(vggp_ctx* ctx, const double* C1, int64_t mv1, const doubl
  * component <= 0, an n_ranks > 1 context, ns > 8192 (covariance), a read-out of cells on a plan that is not Matern-1/2; VGGP_ESTATE for a
  * step without a plan or a read-out before a successful step on the current plan. */
 
+/* Iterative exact GP: the same model as vggp_exact_* at any N >= 1 with N * 64 < 2^31 (along-track data at N ~ 100 000), float64,
+ * single-rank, bitwise repeatable (no floating-point atomics; every reduction in a fixed order).  Sigma = s K0 + sigma2 I is never
+ * stored and takes no jitter: it is applied through vggp_exact_kmv's matrix-free product.  The reference reaches this size through
+ * gpytorch's conjugate gradients and stochastic Lanczos quadrature above max_cholesky_size; this is that recipe with fixed probes.
+ *     preconditioner  Nystroem on r = min(rank, N) strided landmarks idx_j = ((2 j + 1) N) / (2 r) (deterministic: no pivot search):
+ *                     Lz Lz^T = s K0[idx, idx] (psd_safe jitter schedule, vggp_info.jitter1), L = s K0[:, idx] Lz^-T, P = sigma2 I +
+ *                     L L^T, L^T L = V diag(lam) V^T (lam_i <= 1e-14 lam_max dropped), Q = L V lam^-1/2,
+ *                     P^w = sigma2^w (I + Q diag((1 + lam / sigma2)^w - 1) Q^T), log|P| = N log sigma2 + sum log1p(lam / sigma2);
+ *                     rank = 0: P = sigma2 I
+ *     block           column 0: y; columns c >= 1: z_c = P^1/2 z0_c, z0_c Rademacher from the counter hash of the other iterative
+ *                     steps (same seed constant), keyed on (c, i): the same probes on every device, every run
+ *     PCG on Sigma, preconditioner P^-1, per-column stop |r| <= tol |r0|, columns go inactive individually; alpha = x_0
+ *     log|Sigma| ~ log|P| + mean_c N e1^T log(T_c) e1 (T_c: Lanczos tridiagonal of the PCG coefficients of column c)
+ *     tr(Sigma^-1 D) ~ mean_c u_c^T D w_c, u_c = x_c, w_c = P^-1 z_c: ONE derivative-mode product on [alpha, w_1 .. w_p]
+ *     MLL = -1/2 [y^T alpha + log|Sigma| + N log 2 pi], dMLL/d ell_d = (s / 2) [alpha^T d_d K0 alpha - tr_d],
+ *     dMLL/d s1 = (s2 / 2) [alpha^T K0 alpha - tr_K] (s2 symmetric), dMLL/d sigma2 = 1/2 [alpha^T alpha - tr_I]
+ * The MLL and its gradient are ESTIMATES (alpha and y^T alpha are exact to the PCG tolerance): tests/exact_iter_spec.py holds the
+ * same-probe numpy specification and the measured errors.  The workspace is O(N (64 + rank)) doubles, independent of vggp_plan and of
+ * the dense exact workspace, and is replaced by the next vggp_exact_iter_plan.
+ *
+ * vggp_exact_iter_plan: x1, x2 HOST [N] coordinates (finite), kind_d one of VGGP_KIND_*. */
+int vggp_exact_iter_plan(vggp_ctx* ctx, int kind1, int kind2, const double* x1, const double* x2, int64_t N);
+/* y DEVICE [N]; theta as vggp_exact_step.  n_probes <= 0: 16 (at most 63); rank < 0: 64 (at most 256); tol <= 0: 1e-10; max_iter <= 0:
+ * 1000 (gpytorch's max_cg_iterations).  info: jitter1 = the landmark factor's jitter, rounds1 = PCG iterations, sweeps1 = probes.
+ * One value-only product per iteration for the whole block (one host synchronisation per iteration: the count of active columns). */
+int vggp_exact_step_iter(vggp_ctx* ctx, const double* y, const double theta[5], int n_probes, int rank, double tol, int max_iter,
+                         double* mll_out, double grad_out[5], vggp_info* info, void* stream);
+/* posterior(x*) from the state of the last successful iterative step (alpha, theta, Q, lam): xs1, xs2 DEVICE [ns], mean, var DEVICE [ns]
+ * (var NULL: mean only).  mean = s K0(x*, X) alpha, one rectangular product; var = s - s^2 b*^T Sigma^-1 b*, b*_p = K0(X, x*_p) as
+ * explicit [N][64] blocks: ceil(ns / 64) block PCG solves (info: sweeps1 = solves, rounds1 = the largest iteration count).  A column's
+ * numbers do not depend on its neighbours.  There is no dense covariance on this solver. */
+int vggp_exact_posterior_iter(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t ns, double tol, int max_iter, double* mean,
+                              double* var, vggp_info* info, void* stream);
+/* Gridded read-out q(v) as vggp_exact_readout (Matern-1/2 plans; C_d DEVICE [mv_d][N], kd_d DEVICE [mv_d], cells flat a mv2 + b):
+ * mean DEVICE [mv1][mv2] = s C1 diag(alpha) C2^T, one GEMM.  var (may be NULL): with VGGP_READOUT_LITERAL DEVICE [mv1][mv2] =
+ * s kd1 kd2 + s^2 (C1 o C1)(C2 o C2)^T / sigma2, a Gram product without a solve; otherwise the conditional variance at the n_cells
+ * cells of the HOST list `cells`, DEVICE [n_cells], from the block PCG with columns s C1[a] o C2[b]. */
+int vggp_exact_readout_iter(vggp_ctx* ctx, const double* C1, int64_t mv1, const double* C2, int64_t mv2, const double* kd1,
+                            const double* kd2, const int64_t* cells, int64_t n_cells, double tol, int max_iter, double* mean, double* var,
+                            int flags, vggp_info* info, void* stream);
+/* Errors of the iterative exact entries: VGGP_EINVAL for a bad kind, non-finite coordinates, a theta component <= 0, n_probes > 63,
+ * rank > 256, a cell out of range, a conditional variance without cells, cells on a plan that is not Matern-1/2, an n_ranks > 1
+ * context; VGGP_ESTATE without a plan, or for a read-out without a successful step on the current plan; VGGP_ENOCONV when a column
+ * does not converge within max_iter (this ends the state); VGGP_ENOTPD when the landmark factor fails after jitter 1e-6; VGGP_ENOMEM. */
+
 /* building blocks (exported for tests, benchmarks and re-use) ---------------- */
+/* Matrix-free kernel-matrix product of the exact GP's K0 (the building block of an iterative exact solver beyond N = 16384; no plan
+ * needed, single-rank contexts only):
+ *     out0[i][c] = sum_j K0(xr_i, xc_j) V[j][c],  K0(a, b) = k1(|a1 - b1| / ell1) k2(|a2 - b2| / ell2) at unit outputscale,
+ *     out1, out2 = the same with dK0/d ell1 and dK0/d ell2 in the same pass (both NULL: value only; out0 is the same bits either way).
+ * Row points xr1, xr2 DEVICE [Nr], column points xc1, xc2 DEVICE [Nc] (the square case passes the same arrays twice; the rectangular
+ * case is a posterior mean), V DEVICE [Nc][nb] row-major, out* DEVICE [Nr][nb], 1 <= nb <= 64, Nr, Nc in [1, 2^25), kind_d any of
+ * VGGP_KIND_* (mixed pairs included).  K0 is never stored: each lane generates its fragment of v_mfma_f64_16x16x4_f64 from the
+ * coordinates with one exp per element, shared by the value and both derivatives (csrc/exact_iter.hip).  A row's sum over j is taken by
+ * one workgroup in ascending j without atomics: bitwise repeatable.  VGGP_EINVAL for a null context or argument, a bad kind, a
+ * lengthscale <= 0, sizes out of range, only one of out1 / out2, an n_ranks > 1 context. */
+int vggp_exact_kmv(vggp_ctx* ctx, int kind1, int kind2, double ell1, double ell2, const double* xr1, const double* xr2, int64_t Nr,
+                   const double* xc1, const double* xc2, int64_t Nc, const double* V, int64_t nb, double* out0, double* out1, double* out2,
+                   void* stream);
+
 /* Unit-outputscale factor build for one dimension: A0[m][n], dA0/d ell [m][n],
  * K0[m][m], dK0/d ell [m][m] (any output pointer may be NULL).  x DEVICE [n];
  * grid DEVICE ([m+1] mesh for B0, [m] coords for POINTS).

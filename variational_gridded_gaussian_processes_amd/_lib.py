@@ -94,6 +94,11 @@ SYMBOLS = {
     "vggp_exact_posterior": (_I, [_P, _P, _P, _I64, _P, _P, _P]),
     "vggp_exact_posterior_cov": (_I, [_P, _P, _P, _I64, _P, _P]),
     "vggp_exact_readout": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I, _P]),
+    "vggp_exact_iter_plan": (_I, [_P, _I, _I, _P, _P, _I64]),
+    "vggp_exact_step_iter": (_I, [_P, _P, C.POINTER(_D), _I, _I, _D, _I, C.POINTER(_D), C.POINTER(_D), C.POINTER(Info), _P]),
+    "vggp_exact_posterior_iter": (_I, [_P, _P, _P, _I64, _D, _I, _P, _P, C.POINTER(Info), _P]),
+    "vggp_exact_readout_iter": (_I, [_P, _P, _I64, _P, _I64, _P, _P, C.POINTER(_I64), _I64, _D, _I, _P, _P, _I, C.POINTER(Info), _P]),
+    "vggp_exact_kmv": (_I, [_P, _I, _I, _D, _D, _P, _P, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _P]),
     "vggp_factor_build": (_I, [_P, _I, _I, _P, _I64, _P, _I64, _D, _I, _P, _P, _P, _P, _P]),
     "vggp_cholesky_inverse": (_I, [_P, _P, _I64, _P, _P, C.POINTER(_D), _P]),
     "vggp_eigh": (_I, [_P, _P, _I64, _P, _P, C.POINTER(C.c_int32), _I, _P]),

@@ -136,6 +136,7 @@ extern "C" int vggp_destroy(vggp_ctx* c) {
     vg_masked_free(c);
     vg_paired_free(c);
     vg_exact_free(c);
+    vg_exact_iter_free(c);
     vg_comm_destroy(c);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->arena) (void)hipFree(c->arena);

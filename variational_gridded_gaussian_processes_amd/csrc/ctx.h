@@ -133,6 +133,7 @@ struct vggp_ctx {
     double prof_ms[VGGP_NSTAGE] = {};
     int prof_steps = 0;
     void* exact = nullptr;           // VgExact workspace (exact.hip): allocated by vggp_exact_plan, independent of vggp_plan's state
+    void* exact_iter = nullptr;      // VgExactIter workspace (exact_iter.hip): allocated by vggp_exact_iter_plan, independent of both
 };
 
 
@@ -163,6 +164,7 @@ int vg_paired_readout(vggp_ctx* c, const double* C1, int64_t mv1, const double* 
 int vg_paired_posterior(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var, hipStream_t st);
 int vg_paired_posterior_cov(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* cov, hipStream_t st);
 void vg_exact_free(vggp_ctx* c);      // exact GP (exact.hip)
+void vg_exact_iter_free(vggp_ctx* c); // iterative exact GP (exact_iter.hip)
 // entries that have no paired meaning: VGGP_EINVAL with a message
 #define VG_NOT_PAIRED(c, fn)                                                                                            \
     do {                                                                                                                \

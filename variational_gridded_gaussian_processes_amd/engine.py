@@ -84,6 +84,8 @@ class Engine:
         self.plan_token = 0          # bumped by every plan(): a model sharing this engine re-plans when it is not the last planner
         self.exact_n = 0             # points of the current exact plan (exact_plan)
         self.exact_token = 0         # ... and its counter, for the exact models that share this engine
+        self.exact_iter_n = 0        # the same for the iterative exact plan (exact_iter_plan)
+        self.exact_iter_token = 0
 
     @staticmethod
     def unique_id() -> bytes:
@@ -571,6 +573,98 @@ class Engine:
         check(self.lib.vggp_exact_readout(self._h, _ptr(C1), C1.shape[0], _ptr(C2), C2.shape[0], _ptr(kd1), _ptr(kd2), _ptr(mean),
                                           _ptr(var), 1 if literal else 0, _stream(self.device)))
         return mean, var
+
+    # -- iterative exact GP (matrix-free PCG; any N with N * 64 < 2^31; a workspace of its own) --------------
+    def exact_iter_plan(self, kind1: str, kind2: str, x1, x2) -> None:
+        """Iterative exact GP on the N points (x1[k], x2[k]) (vggp_exact_iter_plan).  Independent of plan() and of exact_plan()."""
+        x1, x2 = _dvec(x1), _dvec(x2)
+        if len(x1) != len(x2):
+            raise ValueError("exact plan: x1 and x2 must hold one coordinate pair per point")
+        with torch.cuda.device(self.device):
+            check(self.lib.vggp_exact_iter_plan(self._h, KIND[kind1], KIND[kind2], x1.ctypes.data, x2.ctypes.data, len(x1)))
+        self.exact_iter_n = len(x1)
+        self.exact_iter_token += 1
+
+    def exact_step_iter(self, y: torch.Tensor, theta: Sequence[float], n_probes: int = 0, rank: int = -1, tol: float = 0.0,
+                        max_iter: int = 0):
+        """-> (marginal log likelihood, grad[5], info dict): PCG + stochastic Lanczos quadrature estimates (vggp_exact_step_iter);
+        the defaults (16 probes, rank 64, tol 1e-10, 1000 iterations) are the entry's.  info["rounds"][0] = PCG iterations."""
+        if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == self.exact_iter_n):
+            raise TypeError("y must be a contiguous float64 GPU tensor with one value per planned point")
+        th = (C.c_double * 5)(*[float(t) for t in theta])
+        mll = C.c_double()
+        grad = (C.c_double * 5)()
+        info = Info()
+        check(self.lib.vggp_exact_step_iter(self._h, _ptr(y), th, int(n_probes), int(rank), float(tol), int(max_iter), C.byref(mll), grad,
+                                            C.byref(info), _stream(self.device)))
+        return mll.value, np.array(list(grad)), self._info(info)
+
+    def exact_posterior_iter(self, x_star: torch.Tensor, variance: bool = True, tol: float = 0.0, max_iter: int = 0):
+        """posterior(x*) of the last iterative exact step; x_star [ns, 2] -> mean[ns], var[ns] (None without variance), info."""
+        xs = x_star.to(self.device, torch.float64)
+        xs1, xs2 = xs[:, 0].contiguous(), xs[:, 1].contiguous()
+        ns = xs1.shape[0]
+        mean = torch.empty(ns, dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mean) if variance else None
+        info = Info()
+        check(self.lib.vggp_exact_posterior_iter(self._h, _ptr(xs1), _ptr(xs2), ns, float(tol), int(max_iter), _ptr(mean), _ptr(var),
+                                                 C.byref(info), _stream(self.device)))
+        return mean, var, self._info(info)
+
+    def exact_readout_iter(self, C1: torch.Tensor, C2: torch.Tensor, kd1: torch.Tensor, kd2: torch.Tensor, literal: bool = True, cells=None,
+                           variance: bool = True, tol: float = 0.0, max_iter: int = 0):
+        """Gridded read-out q(v) from the last iterative exact step (Matern-1/2 plans), operands as exact_readout -> mean [mv1, mv2],
+        var, info: literal=True gives var [mv1, mv2] without a solve; literal=False the conditional variance at `cells` [n_cells]."""
+        C1, C2 = C1.to(self.device, torch.float64).contiguous(), C2.to(self.device, torch.float64).contiguous()
+        kd1, kd2 = kd1.to(self.device, torch.float64).contiguous(), kd2.to(self.device, torch.float64).contiguous()
+        n = self.exact_iter_n
+        if C1.shape[1] != n or C2.shape[1] != n or kd1.numel() != C1.shape[0] or kd2.numel() != C2.shape[0]:
+            raise ValueError("C_d must be [mv_d, N] and kd_d [mv_d]")
+        mean = torch.empty(C1.shape[0], C2.shape[0], dtype=torch.float64, device=self.device)
+        cl, ncell = None, 0
+        if cells is not None:
+            idx = np.ascontiguousarray(np.asarray(cells, dtype=np.int64).reshape(-1))
+            cl, ncell = idx.ctypes.data_as(C.POINTER(C.c_int64)), len(idx)
+        var = None
+        if variance:
+            # (never an empty tensor: its null pointer would read as "mean only" and hide a missing cell list from the entry)
+            var = torch.empty_like(mean) if literal else torch.empty(max(ncell, 1), dtype=torch.float64, device=self.device)
+        info = Info()
+        check(self.lib.vggp_exact_readout_iter(self._h, _ptr(C1), C1.shape[0], _ptr(C2), C2.shape[0], _ptr(kd1), _ptr(kd2), cl, ncell,
+                                               float(tol), int(max_iter), _ptr(mean), _ptr(var), 1 if literal else 0, C.byref(info),
+                                               _stream(self.device)))
+        return mean, (var if (var is None or literal) else var[:ncell]), self._info(info)
+
+    def exact_iter_alpha(self, theta: Sequence[float], chunk: int = 2048) -> torch.Tensor:
+        """alpha = Sigma^-1 y of the last iterative exact step [N], read back exactly (diagnostics and tests; Matern-1/2 plans): the
+        gridded read-out's mean s C1 diag(alpha) C2^T with C1 = 1^T and one-hot rows in C2 is s alpha_i, one term per output."""
+        n, s = self.exact_iter_n, float(theta[2]) * float(theta[3])
+        one = torch.ones(1, n, dtype=torch.float64, device=self.device)
+        out = torch.empty(n, dtype=torch.float64, device=self.device)
+        for i0 in range(0, n, chunk):
+            k = min(chunk, n - i0)
+            C2 = torch.zeros(k, n, dtype=torch.float64, device=self.device)
+            C2[torch.arange(k), i0 + torch.arange(k)] = 1.0
+            mean, _, _ = self.exact_readout_iter(one, C2, torch.ones(1), torch.ones(k), variance=False)
+            out[i0:i0 + k] = mean[0] / s
+        return out
+
+    def exact_kmv(self, kind1: str, kind2: str, ell1: float, ell2: float, xr: torch.Tensor, xc: torch.Tensor, V: torch.Tensor,
+                  derivatives: bool = False):
+        """Matrix-free K0(xr, xc) @ V at unit outputscale (vggp_exact_kmv): xr [Nr, 2], xc [Nc, 2], V [Nc, nb] (nb <= 64) float64
+        -> out0 [Nr, nb]; derivatives=True -> (out0, out1, out2) with dK0/d ell1 and dK0/d ell2 in the same pass."""
+        xr, xc = xr.to(self.device, torch.float64), xc.to(self.device, torch.float64)
+        if xr.dim() != 2 or xr.shape[1] != 2 or xc.dim() != 2 or xc.shape[1] != 2:
+            raise ValueError("xr and xc must be (N, 2)")
+        if not (V.is_cuda and V.dtype == torch.float64 and V.is_contiguous() and V.dim() == 2 and V.shape[0] == xc.shape[0]):
+            raise TypeError("V must be a contiguous float64 GPU tensor [Nc, nb]")
+        xr1, xr2, xc1, xc2 = xr[:, 0].contiguous(), xr[:, 1].contiguous(), xc[:, 0].contiguous(), xc[:, 1].contiguous()
+        Nr, Nc, nb = xr.shape[0], xc.shape[0], V.shape[1]
+        outs = [torch.empty(Nr, nb, dtype=torch.float64, device=self.device) for _ in range(3 if derivatives else 1)]
+        check(self.lib.vggp_exact_kmv(self._h, KIND[kind1], KIND[kind2], float(ell1), float(ell2), _ptr(xr1), _ptr(xr2), Nr, _ptr(xc1),
+                                      _ptr(xc2), Nc, _ptr(V), nb, _ptr(outs[0]), _ptr(outs[1]) if derivatives else None,
+                                      _ptr(outs[2]) if derivatives else None, _stream(self.device)))
+        return tuple(outs) if derivatives else outs[0]
 
     # -- building blocks ------------------------------------------------------------------------------
     def factor_build(self, kind: str, basis: str, x: torch.Tensor, grid: torch.Tensor, ell: float, flags: int = 0):

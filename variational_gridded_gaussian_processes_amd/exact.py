@@ -4,11 +4,18 @@
     src/models/exact/bivariate_structure.py:9-173               Matern12GP, Matern32GP, Matern52GP (+ RBFGP, new)
     src/models/sparse/gridded_kronecker_structure.py:21-211     GriddedMatern12ExactGP
 
-kernel = kernel_1 * kernel_2 on active dims 0 and 1, Sigma = K + noise I is an N x N matrix (N <= 16384) that the engine builds from
-the coordinates and factors on the GPU (include/vggp.h, vggp_exact_*).  `log_marginal_likelihood()` returns a differentiable 0-d
-tensor whose value and analytic gradient come from one vggp_exact_step; `mll()` is the same per point, what gpytorch's
-ExactMarginalLogLikelihood returns and the notebooks negate.  Raw parameters, transforms and attribute names are those of the sparse
-classes (models.py).  The reference's non_informative_initialise / informative_initialise of these classes read
+kernel = kernel_1 * kernel_2 on active dims 0 and 1, Sigma = K + noise I.  Two solvers (`solver=`):
+    "dense"      Sigma is an N x N matrix (N <= 16384) that the engine builds from the coordinates and factors on the GPU
+                 (include/vggp.h, vggp_exact_*)
+    "iterative"  Sigma is never stored: a matrix-free kernel-matrix product, preconditioned block conjugate gradients and stochastic
+                 Lanczos quadrature on fixed probes (vggp_exact_*_iter) -- what gpytorch does above max_cholesky_size, at any N the
+                 along-track data has (N ~ 100 000).  The marginal likelihood and its gradient are then estimates (`n_probes`,
+                 `precond_rank`, `cg_tol`, `max_cg_iter`); alpha and the read-outs are exact to the CG tolerance.  posterior() gives the
+                 mean at once and the variance on first access (ceil(N* / 64) block solves); there is no dense covariance.
+    "auto"       dense up to N = 16384 (bit for bit what it always was), iterative above.
+`log_marginal_likelihood()` returns a differentiable 0-d tensor whose value and analytic gradient come from one vggp_exact_step
+(or vggp_exact_step_iter); `mll()` is the same per point, what gpytorch's ExactMarginalLogLikelihood returns and the notebooks
+negate.  Raw parameters, transforms and attribute names are those of the sparse classes (models.py).  The reference's non_informative_initialise / informative_initialise of these classes read
 `self.mean.outputscale` and `self.kernel.outputscale`, which do not exist (they raise there), and are not ported.  There is no CPU
 fallback.
 """
@@ -52,12 +59,21 @@ class GP(torch.nn.Module):
 
     kind = "matern12"
 
+    DENSE_MAX_N = 16384
+
     def __init__(self, train_x: torch.Tensor, train_y: torch.Tensor, likelihood: Optional[GaussianLikelihood] = None,
-                 engine: Optional[Engine] = None):
+                 engine: Optional[Engine] = None, solver: str = "auto", n_probes: int = 16, precond_rank: int = 64, cg_tol: float = 1e-10,
+                 max_cg_iter: int = 1000):
         super().__init__()
         X = torch.as_tensor(train_x)
         if X.dim() != 2 or X.shape[1] != 2:
             raise ValueError("train_x must be (N, 2)")
+        if solver not in ("auto", "dense", "iterative"):
+            raise ValueError("solver must be 'auto', 'dense' or 'iterative'")
+        self.solver = solver
+        self._iterative = solver == "iterative" or (solver == "auto" and X.shape[0] > self.DENSE_MAX_N)
+        self.n_probes, self.precond_rank, self.cg_tol, self.max_cg_iter = int(n_probes), int(precond_rank), float(cg_tol), int(max_cg_iter)
+        self.last_readout_info = None
         self.train_x, self.train_y = train_x, train_y
         self.train_inputs = (train_x,)
         self.train_targets = train_y
@@ -74,6 +90,11 @@ class GP(torch.nn.Module):
         self.last_info = None
 
     def _plan(self):
+        if self._iterative:
+            if self._plan_token != self._engine.exact_iter_token:
+                self._engine.exact_iter_plan(self.kind, self.kind, self._x1, self._x2)
+                self._plan_token = self._engine.exact_iter_token
+            return
         if self._plan_token == self._engine.exact_token:
             return
         self._engine.exact_plan(self.kind, self.kind, self._x1, self._x2)
@@ -83,6 +104,9 @@ class GP(torch.nn.Module):
 
     def _engine_step(self, theta):
         self._plan()
+        if self._iterative:
+            return self._engine.exact_step_iter(self._y, theta, n_probes=self.n_probes, rank=self.precond_rank, tol=self.cg_tol,
+                                                max_iter=self.max_cg_iter)
         return self._engine.exact_step(self._y, theta)
 
     def _refresh(self):
@@ -117,6 +141,14 @@ class GP(torch.nn.Module):
         `.covariance_matrix` is materialised on first access (vggp_exact_posterior_cov, N* <= 8192)."""
         self._refresh()
         xs = torch.as_tensor(x_star, dtype=torch.float64)
+        if self._iterative:              # the mean now (one product); the variance on first access; no dense covariance
+            mean, _, _ = self._engine.exact_posterior_iter(xs, variance=False)
+
+            def var():
+                self._refresh()          # another exact model may have planned the engine since
+                _, v, self.last_readout_info = self._engine.exact_posterior_iter(xs, tol=self.cg_tol, max_iter=self.max_cg_iter)
+                return v.cpu()
+            return MultivariateNormal(mean.cpu(), var)
         mean, var = self._engine.exact_posterior(xs)
 
         def cov():
@@ -152,8 +184,8 @@ class GriddedMatern12ExactGP(Matern12GP):
     features v on an n_b0_splines x n_b0_splines grid given the data (flat index a * nsplines + b)."""
 
     def __init__(self, train_x, train_y, n_b0_splines: int, dim1_grid_lims: Tuple[float, float], dim2_grid_lims: Tuple[float, float],
-                 likelihood: Optional[GaussianLikelihood] = None, engine: Optional[Engine] = None):
-        super().__init__(train_x, train_y, likelihood, engine)
+                 likelihood: Optional[GaussianLikelihood] = None, engine: Optional[Engine] = None, **solver_options):
+        super().__init__(train_x, train_y, likelihood, engine, **solver_options)
         self.n_b0_splines = self.nsplines = n_b0_splines
         self.dim1_grid_lims, self.dim2_grid_lims = dim1_grid_lims, dim2_grid_lims
         self.b0_mesh_1 = torch.linspace(dim1_grid_lims[0], dim1_grid_lims[1], n_b0_splines + 1)
@@ -181,11 +213,22 @@ class GriddedMatern12ExactGP(Matern12GP):
         """:177-191, mean and the diagonal of the covariance.  literal=True: the reference's own expression, in the form
         Kvv + Kvx Kxv / noise it reduces to (vggp.h); literal=False: the conditional variance of v given the data."""
         self._refresh()
+        if self._iterative:
+            if not literal:
+                raise NotImplementedError("the iterative solver has no conditional variance of all cells at once: q_v_cells(cells)")
+            mean, var, self.last_readout_info = self._engine.exact_readout_iter(*self._readout_operands(), literal=True)
+            return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu())
         mean, var = self._engine.exact_readout(*self._readout_operands(), literal=literal)
         return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu())
 
     def q_v_cells(self, cells, literal: bool = False) -> MultivariateNormal:
-        """q_v() at a list of output cells (flat indices a * nsplines + b)."""
+        """q_v() at a list of output cells (flat indices a * nsplines + b); on the iterative solver the conditional variance costs
+        ceil(len(cells) / 64) block solves."""
         idx = torch.as_tensor(cells, dtype=torch.int64).reshape(-1)
+        if self._iterative and not literal:
+            self._refresh()
+            mean, var, self.last_readout_info = self._engine.exact_readout_iter(*self._readout_operands(), literal=False, cells=idx,
+                                                                                 tol=self.cg_tol, max_iter=self.max_cg_iter)
+            return MultivariateNormal(mean.reshape(-1).cpu()[idx], var.cpu())
         qv = self.q_v(literal=literal)
         return MultivariateNormal(qv.mean[idx], qv.variance[idx])
