@@ -17,7 +17,8 @@ specification's own round-off floor of every case: D_case = the largest ELBO / g
 scattered_iter_spec.errors) between the specification as written and (a) wide=True, (b) tol = 1e-12 with maxit = 128; for the steps of
 a kept-basis trajectory also D_basis = the discrepancy after random orthogonal mixing of the basis inside every group of eigenvalues
 closer than 1e-10 lam_max (seed 0, three draws, the largest).  The GPU bound is max(100 D_case, 10 D_basis, 1e-12), never above
-1e-8 (ELBO) / 1e-6 (gradient).  `python tests/masked_iter_spec.py` measures the floors again and rewrites the dict.
+1e-8 (ELBO) / 1e-6 (gradient).  `python tests/masked_iter_spec.py` measures the floors again and rewrites the dict.  JUMPS are the
+sequences on which the engine must give its kept basis up (inside the step, or for the next one); their floors are per step as well.
 
 Measured on one MI355X: the engine against this file ELBO 2e-16 .. 7e-13, gradient 4e-16 .. 5e-13, q(v) mean <= 2e-11, equal iteration
 counts throughout (tests/test_gpu_masked_iter_spec.py has the per-case print-out).
@@ -325,6 +326,16 @@ TRAJ_COUNTS = {
     "t70_pts32": (True, True, False, False, False, False),
     "t96_rbf": (True, True, True, True, True, True),
 }
+# name -> (shape, pair, mask, mask seed, f): step 0 cold at THETA_T, then steps at theta' = THETA_T with both lengthscales times f -- the
+# two branches of the engine's kept-basis policy that the 2 % drift of TRAJ never reaches.  "x" cases: on step 0's basis theta' needs
+# more than step 0's count + 12 iterations, so the engine abandons the kept basis inside the step and returns the cold step; the step
+# after that runs on the basis of that cold solve.  "half": theta' on step 0's basis takes between 4 and 12 iterations more than step 0,
+# so that step is returned as it is and the NEXT one solves cold.
+JUMPS = {
+    "j70_pts32_x2": ("s70", "pts_m32", "bern70", 36, 2.0),
+    "j96_b0_x4": ("s96", "b0_m12", "bern70", 145, 4.0),
+    "j70_pts32_half": ("s70", "pts_m32", "bern70", 36, 0.5),
+}
 
 
 @functools.lru_cache(maxsize=None)
@@ -364,6 +375,32 @@ def traj_spec(name: str) -> tuple:
     return tuple(out)
 
 
+def jump_theta(name: str) -> np.ndarray:
+    th = THETA_T.copy()
+    th[:2] *= JUMPS[name][4]
+    return th
+
+
+def jump_plan(name: str) -> tuple:
+    """(theta, index of the earlier step whose basis is kept or None for a cold solve) of the steps the engine must take."""
+    th = jump_theta(name)
+    if name.endswith("_half"):
+        return (THETA_T, None), (th, 0), (th, None)
+    return (THETA_T, None), (th, None), (th, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def jump_spec(name: str) -> tuple:
+    """-> (the steps of jump_plan, theta' on step 0's basis: what the engine tries first on its step 1)."""
+    shape, pair, mkind, mseed, _ = JUMPS[name]
+    _, _, f1, f2, _, _, Y, W = problem(shape, pair, mkind, mseed)
+    out = []
+    for th, src in jump_plan(name):
+        out.append(elbo_step_masked_iter(Y, W, f1, f2, th, basis=None if src is None else (out[src].Q1, out[src].Q2)))
+    kept0 = out[1] if name.endswith("_half") else elbo_step_masked_iter(Y, W, f1, f2, jump_theta(name), basis=(out[0].Q1, out[0].Q2))
+    return tuple(out), kept0
+
+
 def _disc(a: MaskedIterSpecState, b: MaskedIterSpecState) -> float:
     return max(errors(b.elbo, b.grad, a.elbo, a.grad, a.N))
 
@@ -390,6 +427,22 @@ def floor_traj(name: str) -> list:
         dc = max(_disc(st, elbo_step_masked_iter(Y, W, f1, f2, th, basis=basis, wide=True)),
                  _disc(st, elbo_step_masked_iter(Y, W, f1, f2, th, basis=basis, tol=1e-12, maxit=128)))
         db = max(_disc(st, elbo_step_masked_iter(Y, W, f1, f2, th, basis=mb)) for mb in mixed) if basis is not None else 0.0
+        out.append((dc, db))
+    return out
+
+
+def floor_jump(name: str) -> list:
+    """[(D_case, D_basis)] of the steps of a jump (floor_traj's two quantities, the basis mixed being the one that step keeps)."""
+    shape, pair, mkind, mseed, _ = JUMPS[name]
+    _, _, f1, f2, _, _, Y, W = problem(shape, pair, mkind, mseed)
+    sts, _ = jump_spec(name)
+    rng = np.random.default_rng(0)
+    out = []
+    for st, (th, src) in zip(sts, jump_plan(name)):
+        basis = None if src is None else (sts[src].Q1, sts[src].Q2)
+        dc = max(_disc(st, elbo_step_masked_iter(Y, W, f1, f2, th, basis=basis, wide=True)),
+                 _disc(st, elbo_step_masked_iter(Y, W, f1, f2, th, basis=basis, tol=1e-12, maxit=128)))
+        db = 0.0 if src is None else max(_disc(st, elbo_step_masked_iter(Y, W, f1, f2, th, basis=mixed_basis(sts[src], rng))) for _ in range(3))
         out.append((dc, db))
     return out
 
@@ -422,6 +475,9 @@ FLOORS = {
     't96_b0': [(6.33e-13, 0.00e+00), (7.93e-13, 0.00e+00), (6.90e-13, 0.00e+00), (6.27e-13, 0.00e+00), (1.10e-12, 0.00e+00), (1.45e-12, 0.00e+00)],
     't70_pts32': [(1.71e-11, 0.00e+00), (1.87e-11, 0.00e+00), (6.13e-12, 0.00e+00), (4.02e-12, 0.00e+00), (4.45e-12, 0.00e+00), (4.16e-12, 0.00e+00)],
     't96_rbf': [(1.33e-11, 0.00e+00), (1.54e-11, 0.00e+00), (1.79e-11, 0.00e+00), (2.09e-11, 0.00e+00), (2.50e-11, 0.00e+00), (3.81e-11, 0.00e+00)],
+    'j70_pts32_x2': [(1.71e-11, 0.00e+00), (2.22e-10, 0.00e+00), (2.22e-10, 0.00e+00)],
+    'j96_b0_x4': [(6.33e-13, 0.00e+00), (1.46e-11, 0.00e+00), (1.46e-11, 0.00e+00)],
+    'j70_pts32_half': [(1.71e-11, 0.00e+00), (3.83e-12, 0.00e+00), (5.59e-12, 0.00e+00)],
 }
 # FLOORS-END
 
@@ -432,6 +488,8 @@ def _regenerate():
         lines.append(f"    {name!r}: {floor_case(name):.2e},")
     for name in TRAJ:
         lines.append(f"    {name!r}: [" + ", ".join(f"({dc:.2e}, {db:.2e})" for dc, db in floor_traj(name)) + "],")
+    for name in JUMPS:
+        lines.append(f"    {name!r}: [" + ", ".join(f"({dc:.2e}, {db:.2e})" for dc, db in floor_jump(name)) + "],")
     lines.append("}")
     path = os.path.abspath(__file__)
     src = open(path).read()

@@ -4,7 +4,8 @@ round-off floor and not the estimator's noise -- max(100 D_case, 10 D_basis, 1e-
 1e-6 (gradient).  Cold steps after a fresh plan on 96 x 80, 70 x 45 and 200 x 130 grids (every basis / kernel pair, mask and probe
 count of masked_iter_spec.CASES) with equal iteration counts, the probe count as info['sweeps'][0], the q(v) mean at 1e-9 and calls
 two and three bitwise equal; six steps of one plan (theta (1 + 0.02 k)) against the specification on the basis of ITS step 0 (Rayleigh
-quotients) and, for RBF, cold at every step; the probe limit.
+quotients) and, for RBF, cold at every step; jumps in theta that make the engine give its kept basis up (inside the step, or for
+the next one); the probe limit.
 
 Measured on one MI355X: iteration counts equal in every case and step (1 .. 34); ELBO 2e-16 .. 7e-13, gradient 4e-16 .. 5e-13
 (bounds 1e-12 .. 8e-9), q(v) mean 4e-15 .. 2e-11; all ones against vggp_elbo_step 1e-14 (96 x 80) and 5e-12 / 2e-12 (200 x 130).  Under
@@ -96,6 +97,42 @@ def test_trajectory_vs_spec(engine, name):
         assert e_grad <= b_grad, k
         e_q = rel(engine.qv_masked_iter(W, nobs, variance=False)[0].cpu().numpy(), MS.qv_mean(st, f1, f2))
         assert e_q <= 1e-9, k
+
+
+@pytest.mark.parametrize("name", list(MS.JUMPS))
+def test_jump_in_theta_vs_spec(engine, name):
+    """The two branches of the kept-basis policy that a 2 % drift never reaches (masked_iter_spec.JUMPS).  "x": on step 0's basis the
+    new theta would take more than step 0's count + 12 iterations, so step 1 gives the basis up and returns the COLD step; step 2
+    keeps the basis of that cold solve, step 3 equals step 2 bit for bit.  "half": step 1 stands on step 0's basis with between 4 and 12
+    iterations more than step 0, so step 2 solves cold.  The stopping margins hold on step 0 only: later counts within 1."""
+    shape, pair, mkind, mseed, _ = MS.JUMPS[name]
+    d1, d2, f1, f2, x1, x2, Y, Wn = MS.problem(shape, pair, mkind, mseed)
+    sts, _ = MS.jump_spec(name)
+    Ym, W, nobs, yy = _plan(engine, d1, d2, x1, x2, Y, Wn)
+    half = name.endswith("_half")
+    got = []
+    for k, (st, (theta, src)) in enumerate(zip(sts, MS.jump_plan(name))):
+        elbo, grad, info = engine.elbo_step_masked_iter(Ym, W, nobs, yy, theta)
+        got.append((elbo, grad, info))
+        e_elbo, e_grad = MS.errors(elbo, grad, st.elbo, st.grad, st.N)
+        b_elbo, b_grad = MS.bounds(*MS.FLOORS[name][k])
+        e_q = rel(engine.qv_masked_iter(W, nobs, variance=False)[0].cpu().numpy(), MS.qv_mean(st, f1, f2))
+        print(f"{name} step {k} ({'cold' if src is None else f'basis of step {src}'}): iterations {info['rounds'][0]} (spec {st.iters}); "
+              f"ELBO {e_elbo:.2e} (bound {b_elbo:.2e}) gradient {e_grad:.2e} (bound {b_grad:.2e}) q(v) mean {e_q:.2e}")
+        assert info["status"] == 0 and info["sweeps"][0] == 16
+        if k == 0:
+            assert info["rounds"][0] == st.iters
+        else:
+            assert abs(info["rounds"][0] - st.iters) <= 1
+        assert e_elbo <= b_elbo, k
+        assert e_grad <= b_grad, k
+        assert e_q <= 1e-9, k
+    if half:
+        assert got[1][2]["rounds"][0] > got[0][2]["rounds"][0] + 4          # ... which is why step 2 solved cold
+    else:
+        assert got[1][2]["rounds"][0] <= got[0][2]["rounds"][0] + 12        # the cold step, not an iteration on the stale basis
+        e3, g3, i3 = engine.elbo_step_masked_iter(Ym, W, nobs, yy, MS.jump_theta(name))
+        assert e3 == got[2][0] and np.array_equal(g3, got[2][1]) and i3["rounds"] == got[2][2]["rounds"]
 
 
 def test_probe_limit(engine):

@@ -9,6 +9,9 @@ tests/test_gpu_masked_iter_spec.py stands on.
   * the stopping margins hold in every column of every cold case (last ratio <= 0.5, the one before >= 2): only then may the GPU test
     assert equal iteration counts; for the trajectories the table TRAJ_COUNTS says step by step where they do, and the steps stay inside
     the engine's rule for keeping a basis (at most 4 iterations more than right after the cold solve);
+  * the jumps (JUMPS): on step 0's basis the new theta takes at least 12 + 4 iterations more than step 0 ("x": the engine gives the
+    kept basis up inside the step) or between 4 + 2 and 12 - 2 more ("half": the step stands and the next one solves cold), so that the
+    GPU test knows which branch of the engine's policy each step takes;
   * the round-off floors: recomputed, none above twice the committed value, and 100 D_case never above the caps 1e-8 / 1e-6.
 """
 import os
@@ -121,8 +124,25 @@ def test_trajectories(name):
         assert not np.array_equal(sts[1].Q1, sts[0].Q1)
 
 
+@pytest.mark.parametrize("name", list(MS.JUMPS))
+def test_jumps_take_the_branch_they_are_named_for(name):
+    sts, kept0 = MS.jump_spec(name)
+    its = [s.iters for s in sts]
+    print(f"{name}: iterations {its}, theta' on step 0's basis {kept0.iters}")
+    assert len(sts) == 3 and all(s.converged for s in sts) and kept0.converged
+    assert sts[0].margins_ok()                 # step 0: the GPU test asserts the equal count
+    assert np.array_equal(sts[0].theta, MS.THETA_T) and np.array_equal(sts[1].theta[:2], MS.THETA_T[:2] * MS.JUMPS[name][4])
+    if name.endswith("_half"):                 # kept, no retry (<= reference + 12); the next step solves cold (> reference + 4)
+        assert its[0] + 4 + 2 <= kept0.iters <= its[0] + 12 - 2
+        assert kept0 is sts[1] and np.array_equal(sts[1].Q1, sts[0].Q1) and not np.array_equal(sts[2].Q1, sts[0].Q1)
+    else:                                      # given up inside the step (> reference + 12), and the cold step stays clear of the limit
+        assert kept0.iters >= its[0] + 12 + 4
+        assert its[1] + 1 <= its[0] + 12
+        assert np.array_equal(sts[2].Q1, sts[1].Q1) and np.array_equal(sts[2].Q2, sts[1].Q2) and not np.array_equal(sts[1].Q1, sts[0].Q1)
+
+
 def test_floors_against_the_committed_table():
-    assert set(MS.FLOORS) == set(MS.CASES) | set(MS.TRAJ)
+    assert set(MS.FLOORS) == set(MS.CASES) | set(MS.TRAJ) | set(MS.JUMPS)
     for name in MS.CASES:
         d = MS.floor_case(name)
         print(f"{name}: D_case {d:.2e} (committed {MS.FLOORS[name]:.2e}) -> bounds {MS.bounds(MS.FLOORS[name])}")
@@ -133,4 +153,11 @@ def test_floors_against_the_committed_table():
             print(f"{name} step {k}: D_case {dc:.2e} ({rc:.2e}) D_basis {db:.2e} ({rb:.2e})")
             assert dc <= 2.0 * rc and db <= 2.0 * rb, (name, k)
             assert max(100.0 * rc, 10.0 * rb) <= MS.CAP_ELBO, (name, k)
+    for name in MS.JUMPS:          # (100 D_case of a cold step at a doubled lengthscale may reach the ELBO cap: bounds() then gives the cap)
+        assert len(MS.FLOORS[name]) == 3
+        for k, ((dc, db), (rc, rb)) in enumerate(zip(MS.floor_jump(name), MS.FLOORS[name])):
+            print(f"{name} step {k}: D_case {dc:.2e} ({rc:.2e}) D_basis {db:.2e} ({rb:.2e})")
+            assert dc <= 2.0 * rc and db <= 2.0 * rb, (name, k)
+            assert max(100.0 * rc, 10.0 * rb) <= MS.CAP_GRAD, (name, k)
+            assert MS.bounds(rc, rb)[0] <= MS.CAP_ELBO and MS.bounds(rc, rb)[1] <= MS.CAP_GRAD, (name, k)
     assert MS.bounds(0.0) == (1e-12, 1e-12) and MS.bounds(1.0) == (MS.CAP_ELBO, MS.CAP_GRAD) and MS.bounds(1e-13, 1e-11)[0] == pytest.approx(1e-10)

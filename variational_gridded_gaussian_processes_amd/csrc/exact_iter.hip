@@ -10,6 +10,7 @@
 // Every product of two kernels is a polynomial in a = |d1| / ell1, b = |d2| / ell2 times ONE exp of the summed exponents, and both
 // length-scale derivatives share it; the kernel kinds are template parameters (dispatch per launch, nothing per element).
 #include "ctx.h"
+#include "lanczos_quad.h"
 
 #include <cmath>
 
@@ -515,45 +516,9 @@ static int exi_pcg(VgExactIter& w, int nbp, int ncols, double tol, int max_iter,
     *nact_out = nact;
     return VGGP_OK;
 }
-// e1^T log(T) e1 of the k x k Lanczos tridiagonal (implicit QL with shifts, first eigenvector components only: vgi_slq_kernel)
+// e1^T log(T) e1 of the k x k Lanczos tridiagonal (lanczos_quad.h: the routine of vgi_slq_kernel); false: the quadrature failed
 static bool exi_slq(std::vector<double>& d, std::vector<double>& e, std::vector<double>& z, int k, double* out) {
-    for (int l = 0; l < k; ++l) {
-        int iter = 0, mm;
-        do {
-            for (mm = l; mm < k - 1; ++mm) {
-                const double dd = fabs(d[mm]) + fabs(d[mm + 1]);
-                if (fabs(e[mm]) <= 1e-16 * dd) break;
-            }
-            if (mm != l) {
-                if (iter++ == 60) return false;
-                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-                double r = hypot(g, 1.0);
-                g = d[mm] - d[l] + e[l] / (g + (g >= 0.0 ? fabs(r) : -fabs(r)));
-                double s = 1.0, cc = 1.0, p = 0.0;
-                int i;
-                for (i = mm - 1; i >= l; --i) {
-                    double f = s * e[i];
-                    const double b = cc * e[i];
-                    e[i + 1] = (r = hypot(f, g));
-                    if (r == 0.0) { d[i + 1] -= p; e[mm] = 0.0; break; }
-                    s = f / r; cc = g / r;
-                    g = d[i + 1] - p;
-                    r = (d[i] - g) * s + 2.0 * cc * b;
-                    d[i + 1] = g + (p = s * r);
-                    g = cc * r - b;
-                    f = z[i + 1];
-                    z[i + 1] = s * z[i] + cc * f;
-                    z[i] = cc * z[i] - s * f;
-                }
-                if (r == 0.0 && i >= l) continue;
-                d[l] -= p; e[l] = g; e[mm] = 0.0;
-            }
-        } while (mm != l);
-    }
-    double acc = 0.0;
-    for (int j = 0; j < k; ++j) { if (!(d[j] > 0.0)) return false; acc += z[j] * z[j] * log(d[j]); }
-    *out = acc;
-    return true;
+    return vg_lanczos_logquad(d.data(), e.data(), z.data(), k, out) == 0;
 }
 
 static void exi_fill_info(vggp_info* info, double jit, int sweeps, int rounds, int status) {

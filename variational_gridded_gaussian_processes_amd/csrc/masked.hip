@@ -13,6 +13,7 @@
 //              inverse of the factor and Sigma~^{-1} = L^{-T} L^{-1} by GEMM
 //   gradient   analytic, from Sigma~^{-1}, its partial traces, <Sigma~^{-1}, Phi~'_d> and three n2 x n1 products.
 #include "ctx.h"
+#include "lanczos_quad.h"
 
 #include <algorithm>
 
@@ -1053,21 +1054,23 @@ extern "C" int vggp_qv_cov_masked(vggp_ctx* c, double* cov, void* stream) {
 //                   the probe z = P^1/2 z0, z0 Rademacher from a counter-based hash (bitwise reproducible)
 //   traces          tr(Sigma~^-1 D) = tr(P^-1 D) [closed form, two GEMMs over the mask] + mean_z (Sigma~^-1 z - P^-1 z)^T D P^-1 z
 // ================================================================================================================================
+#define VGI_NTS 16                                // the scalars vgi_combine_kernel reads (14 used)
 struct VgIter {
     int nbc = 0, maxit = 0;
-    double *Wt;                                   // [n1][n2] mask, transposed once per step
+    double *Wt;                                   // [n1][n2] mask, transposed once per step (masked data only)
     double *X, *R, *Zp, *Pd, *AP, *Wz, *Tm, *Tm2; // block vectors [m1][nbc][m2]
-    double *T1;                                   // [n1][nbc][max(m1, m2)]
-    double *F0, *F1, *F2;                         // fields [n1][nbc][n2]
+    double *T1;                                   // [n1][nbc][max(m1, m2)] (masked data only)
+    double *F0, *F1, *F2;                         // fields [n1][nbc][n2]; scattered points: [nbc][N]
     double *alh, *beh;                            // [maxit][nbc] PCG coefficients
     double *col;                                  // per-column scalars: [0] rz, [1] pAp, [2] r0^2, [3] rr, [4] alpha, [5] beta, [6] active, [7] k
     double *Rr1, *Rr2, *Rv1, *Rv2, *RR1, *RRV1, *RR2, *RRV2, *TW, *TWv, *Ex;   // rotated factors and the exact traces' temporaries
     double *dg1, *dg2, *Tq;                       // diag(Q^T Mk Q), m x m temporary
     double *Qk1, *Qk2;                            // the preconditioner's eigenbasis of the last cold solve (rows = eigenvectors), kept across steps
-    double *ts;                                   // [32] scalars
-    double *fpart;                                // [1024] block partials of the field sums (masked step)
+    double *ts;                                   // [VGI_NTS] scalars
+    double *pc;                                   // [nbc] per-column sums: the probes' quadratures, later the column dots of the Mk terms
+    double *fpart;                                // [1024] block partials of the field sums
+    double *krs;                                  // scattered points: split scratch of the back kernel
     int* nact;                                    // device word: number of active columns
-    int* h_nact;                                  // pinned
 };
 
 __device__ __forceinline__ unsigned long long vgi_mix(unsigned long long x) {       // splitmix64 finaliser
@@ -1196,8 +1199,9 @@ __global__ void vgi_rowdot_kernel(const double* A, const double* B, int m, doubl
     for (int k = 0; k < m; ++k) s += A[(long)a * m + k] * B[(long)a * m + k];
     out[a] = s;
 }
-// Gauss quadrature of log on the Lanczos tridiagonal of each probe column (implicit QL with shifts, first eigenvector components
-// only): one lane per probe, k <= VGI_MAXIT.  out[c - 1] = M sum_j tau_j^2 log(theta_j)
+// Gauss quadrature of log on the Lanczos tridiagonal of each probe column (vg_lanczos_logquad: implicit QL with shifts, first
+// eigenvector components only): one lane per probe, k <= VGI_MAXIT.  out[c - 1] = M sum_j tau_j^2 log(theta_j), nbc - 1 values;
+// fail |= 1: an eigenvalue did not converge, 2: an eigenvalue is not positive
 #define VGI_MAXIT 128
 __global__ void vgi_slq_kernel(const double* alh, const double* beh, const double* col, int nbc, double Mdim, double* out, int* fail) {
     const int c = 1 + blockIdx.x * blockDim.x + threadIdx.x;
@@ -1210,41 +1214,9 @@ __global__ void vgi_slq_kernel(const double* alh, const double* beh, const doubl
         e[j] = j + 1 < k ? sqrt(beh[(long)j * nbc + c]) / a : 0.0;
         z[j] = j == 0 ? 1.0 : 0.0;
     }
-    for (int l = 0; l < k; ++l) {
-        int iter = 0, mm;
-        do {
-            for (mm = l; mm < k - 1; ++mm) {
-                const double dd = fabs(d[mm]) + fabs(d[mm + 1]);
-                if (fabs(e[mm]) <= 1e-16 * dd) break;
-            }
-            if (mm != l) {
-                if (iter++ == 60) { atomicOr(fail, 1); break; }
-                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
-                double r = hypot(g, 1.0);
-                g = d[mm] - d[l] + e[l] / (g + (g >= 0.0 ? fabs(r) : -fabs(r)));
-                double s = 1.0, cc = 1.0, p = 0.0;
-                int i;
-                for (i = mm - 1; i >= l; --i) {
-                    double f = s * e[i];
-                    const double b = cc * e[i];
-                    e[i + 1] = (r = hypot(f, g));
-                    if (r == 0.0) { d[i + 1] -= p; e[mm] = 0.0; break; }
-                    s = f / r; cc = g / r;
-                    g = d[i + 1] - p;
-                    r = (d[i] - g) * s + 2.0 * cc * b;
-                    d[i + 1] = g + (p = s * r);
-                    g = cc * r - b;
-                    f = z[i + 1];
-                    z[i + 1] = s * z[i] + cc * f;
-                    z[i] = cc * z[i] - s * f;
-                }
-                if (r == 0.0 && i >= l) continue;
-                d[l] -= p; e[l] = g; e[mm] = 0.0;
-            }
-        } while (mm != l);
-    }
-    double acc = 0.0;
-    for (int j = 0; j < k; ++j) { if (!(d[j] > 0.0)) atomicOr(fail, 2); acc += z[j] * z[j] * log(d[j]); }
+    double acc;
+    const int code = vg_lanczos_logquad(d, e, z, k, &acc);
+    if (code) atomicOr(fail, code);
     out[c - 1] = Mdim * acc;
 }
 // scalars of the iterative step -> the slots of the dense step's reduction buffer (vgm_final_kernel reads them)
@@ -1303,48 +1275,75 @@ __global__ void vgi_sum_kernel(const double* part, int n, double* out, int c_fro
     out[0] = s;
 }
 
-static int vgi_prepare(vggp_ctx* c, VgMasked& w, VgIter& it, int nbc, int maxit) {
-    const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M, mx = std::max(m1, m2);
-    size_t off = 0;
+// Two-pass arena carver.  `layout` asks for its buffers with take() in a fixed order and is called twice: first to measure (take()
+// hands out null), then, once *mem holds that many bytes, to receive 256-byte-aligned slices of it.  *grew: the arena was too small and
+// has been replaced, so whatever it kept is gone.  oom: a format with two %.1f (GiB needed, GiB free) for the VGGP_ENOMEM raised when
+// the device has less free memory than the arena needs; null: no such check, a failing hipMalloc speaks for itself.
+struct VgArena {
     char* base = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-        off = 0;
-        auto take = [&](size_t count) {
-            off = (off + 255) & ~size_t(255);
-            double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-            off += count * sizeof(double);
-            return p;
-        };
-        it.Wt = take(n1 * n2);
-        it.X = take(M * nbc); it.R = take(M * nbc); it.Zp = take(M * nbc); it.Pd = take(M * nbc); it.AP = take(M * nbc);
-        it.Wz = take(M * nbc); it.Tm = take(M * nbc); it.Tm2 = take(M * nbc);
-        it.T1 = take(n1 * nbc * mx);
-        it.F0 = take(n1 * nbc * n2); it.F1 = take(n1 * nbc * n2); it.F2 = take(n1 * nbc * n2);
-        it.alh = take((size_t)maxit * nbc); it.beh = take((size_t)maxit * nbc);
-        it.col = take(8 * (size_t)nbc);
-        it.Rr1 = take(m1 * n1); it.Rv1 = take(m1 * n1); it.RR1 = take(m1 * n1); it.RRV1 = take(m1 * n1);
-        it.Rr2 = take(m2 * n2); it.Rv2 = take(m2 * n2); it.RR2 = take(m2 * n2); it.RRV2 = take(m2 * n2);
-        it.TW = take(n1 * m2); it.TWv = take(n1 * m2); it.Ex = take(M);
-        it.dg1 = take(m1); it.dg2 = take(m2); it.Tq = take(mx * mx);
-        it.Qk1 = take(m1 * m1); it.Qk2 = take(m2 * m2);
-        it.ts = take(64);
-        it.nact = reinterpret_cast<int*>(take(8));
-        it.fpart = take(1024);                    // (its own: a block vector has M nbc doubles, which may be fewer than the 1024 partials)
-        if (pass == 0) {
-            const size_t need = off + 4096;
-            if (w.ibytes < need || w.ib_nbc != nbc || w.ib_maxit != maxit) w.ib_valid = false;      // (the layout moves: the kept basis is gone)
-            w.ib_nbc = nbc; w.ib_maxit = maxit;
-            if (w.ibytes < need) {
-                if (w.imem) { VG_HIP(hipFree(w.imem)); w.imem = nullptr; w.ibytes = 0; }
-                VG_HIP(hipMalloc(&w.imem, need));
-                w.ibytes = need;
-            }
-            base = reinterpret_cast<char*>(w.imem);
-        }
+    size_t off = 0;
+    double* take(size_t count) {
+        off = (off + 255) & ~size_t(255);
+        double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
+        off += count * sizeof(double);
+        return p;
     }
-    it.nbc = nbc; it.maxit = maxit;
-    (void)c;
+};
+template <class Layout>
+static int vg_arena_carve(void** mem, size_t* bytes, const char* oom, bool* grew, Layout&& layout) {
+    VgArena a;
+    layout(a);
+    const size_t need = a.off + 4096;
+    *grew = *bytes < need;
+    if (*grew) {
+        if (*mem) { VG_HIP(hipFree(*mem)); *mem = nullptr; *bytes = 0; }
+        size_t free_b = 0, total_b = 0;
+        if (oom && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
+            vg_set_error(oom, (double)need / 1073741824.0, (double)free_b / 1073741824.0);
+            return VGGP_ENOMEM;
+        }
+        VG_HIP(hipMalloc(mem, need));
+        *bytes = need;
+    }
+    a.base = reinterpret_cast<char*>(*mem);
+    a.off = 0;
+    layout(a);
     return VGGP_OK;
+}
+
+// The step's arena (w.imem) for either data kind.  Scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N],
+// rotated factors [m_d][N], the back kernel's split scratch.
+static int vgi_prepare(VgMasked& w, VgIter& it, int nbc, int maxit) {
+    const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.scattered ? w.n1 : w.n2, M = w.M, mx = std::max(m1, m2);
+    const bool sc = w.scattered;
+    const size_t nf = sc ? n1 * nbc : n1 * nbc * n2;
+    char oom[256];
+    snprintf(oom, sizeof(oom), "the workspace of the iterative scattered step needs %%.1f GiB (m1 = %d, m2 = %d, N = %ld, %d columns) but only "
+             "%%.1f GiB of device memory are free", w.m1, w.m2, (long)n1, nbc);
+    bool grew = false;
+    const int rc = vg_arena_carve(&w.imem, &w.ibytes, sc ? oom : nullptr, &grew, [&](VgArena& a) {
+        it.Wt = a.take(sc ? 0 : n1 * n2);
+        it.X = a.take(M * nbc); it.R = a.take(M * nbc); it.Zp = a.take(M * nbc); it.Pd = a.take(M * nbc); it.AP = a.take(M * nbc);
+        it.Wz = a.take(M * nbc); it.Tm = a.take(M * nbc); it.Tm2 = a.take(M * nbc);
+        it.T1 = a.take(sc ? 0 : n1 * nbc * mx);
+        it.F0 = a.take(nf); it.F1 = a.take(nf); it.F2 = a.take(nf);
+        it.alh = a.take((size_t)maxit * nbc); it.beh = a.take((size_t)maxit * nbc);
+        it.col = a.take(8 * (size_t)nbc);
+        it.Rr1 = a.take(m1 * n1); it.Rv1 = a.take(m1 * n1); it.RR1 = a.take(m1 * n1); it.RRV1 = a.take(m1 * n1);
+        it.Rr2 = a.take(m2 * n2); it.Rv2 = a.take(m2 * n2); it.RR2 = a.take(m2 * n2); it.RRV2 = a.take(m2 * n2);
+        it.TW = a.take(sc ? 0 : n1 * m2); it.TWv = a.take(sc ? 0 : n1 * m2); it.Ex = a.take(M);
+        it.dg1 = a.take(m1); it.dg2 = a.take(m2); it.Tq = a.take(mx * mx);
+        it.Qk1 = a.take(m1 * m1); it.Qk2 = a.take(m2 * m2);
+        it.ts = a.take(VGI_NTS);
+        it.pc = a.take((size_t)nbc);
+        it.fpart = a.take(1024);                  // (its own: a block vector has M nbc doubles, which may be fewer than the 1024 partials)
+        it.krs = a.take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
+        it.nact = reinterpret_cast<int*>(a.take(8));
+    });
+    if (grew || w.ib_nbc != nbc || w.ib_maxit != maxit) w.ib_valid = false;      // (the layout moves: the kept basis is gone)
+    w.ib_nbc = nbc; w.ib_maxit = maxit;
+    it.nbc = nbc; it.maxit = maxit;
+    return rc;
 }
 
 // G = L^T-side product: block field F[i][c][j] = l_i^T V_c r_j for all columns (V block [m1][nbc][m2], L: m1 x n1, R: m2 x n2)
@@ -1381,20 +1380,288 @@ static int vgi_rot(vggp_ctx* c, const VgMasked& w, const VgIter& it, const doubl
     return gemm1(d1.Qt, 1, m1, it.Tm, (long)nbc * m2, 1, out, nbc * m2, m1, nbc * m2, m1, st);                     // Q1 (.)
 }
 
+// ---- the stages both iterative steps (and the block solves of their read-outs) are made of --------------------------------------------
+// AP = Pd + rho Phi~ Pd for the block.  Masked grid: Phi~ V = B1 (Wt o (B1^T V B2)) B2^T.  Scattered points (w.scattered):
+// Phi~ V = sum_k b1_k (b1_k^T V b2_k) b2_k^T by the two kernels of kr.hip, the field kernel in its four-column instantiation or
+// (field2) in its two-column one: the same bits at 2.2 x the rate at 64 columns and at 16; the read-outs run that one
+static int vgi_apply(vggp_ctx* c, const VgMasked& w, const VgIter& it, bool field2, hipStream_t st) {
+    const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
+    const long n1 = w.n1, n2 = w.n2, nb = w.M * nbc;
+    const double *B1 = c->d[0].BV, *B2 = c->d[1].BV;
+    int rc;
+    if (w.scattered) {
+        if (field2) VG_HIP(vg_kr_field2_launch(B1, B2, it.Pd, m1, m2, n1, nbc, it.F0, st));
+        else VG_HIP(vg_kr_field_launch(B1, B2, it.Pd, m1, m2, n1, nbc, it.F0, st));
+        VG_HIP(vg_kr_back_launch(B1, B2, it.F0, m1, m2, n1, nbc, it.AP, it.krs, st));
+    } else {
+        if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
+        VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
+        if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
+    }
+    VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
+    return VGGP_OK;
+}
+
 #define VGI_ESTALE (-1001)      // internal: the kept preconditioner basis is too far off (the caller repeats the step with a cold solve)
-static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs, const double theta[5],
-                            int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream);
-extern "C" int vggp_elbo_step_masked_iter(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs, const double theta[5],
-                                          int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5], vggp_info* info,
-                                          void* stream) {
-    VG_NOT_PAIRED(c, "vggp_elbo_step_masked_iter");
-    int rc = masked_iter_once(c, Ym, W, n_obs, yy_obs, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
-    if (rc == VGI_ESTALE) rc = masked_iter_once(c, Ym, W, n_obs, yy_obs, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
-    if (rc == VGI_ESTALE) { vg_set_error("vggp_elbo_step_masked_iter: internal (stale basis after a cold solve)"); rc = VGGP_ESTATE; }
+// Block PCG for Sigma~ X = R: the right-hand sides are in it.R on entry (zero columns start inactive), the solution is in it.X on
+// return; preconditioner from d.Qt, d.lam0 and p, per-column stopping rule.  history: iteration k keeps its coefficients in row k of
+// alh / beh (the quadrature reads them) instead of overwriting row 0.  stale_limit > 0: a solve that still has active columns after
+// more iterations than that gives the kept basis up (VGI_ESTALE).  One host read-back of the active count per iteration.
+static int vgi_pcg(vggp_ctx* c, VgMasked& w, const VgIter& it, double p, double tol, int max_iter, bool history, bool field2, int stale_limit,
+                   int* iters_out, int* nact_out, hipStream_t st) {
+    const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
+    const long nb = w.M * nbc;
+    int rc;
+    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
+    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
+    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, m1, nbc, m2, it.col, it.col + 3 * nbc);
+    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
+    int iters = 0, nact = nbc;
+    for (int k = 0; k < max_iter && nact > 0; ++k) {
+        const int row = history ? k : 0;
+        if ((rc = vgi_apply(c, w, it, field2, st))) return rc;
+        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, m1, nbc,
+                           m2, it.col + nbc, (double*)nullptr);
+        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, row, tol, it.alh, it.beh, it.nact);
+        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, m1, nbc, m2, 1);
+        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
+        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, m1, nbc, m2, it.col + 5 * nbc,
+                           it.col + 3 * nbc);
+        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, row, tol, it.alh, it.beh, it.nact);
+        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, m1, nbc, m2, 2);
+        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipStreamSynchronize(st));
+        nact = c->h_out->counters[0][0];
+        iters = k + 1;
+        if (stale_limit > 0 && nact > 0 && iters > stale_limit) {      // the kept basis has drifted too far: not worth iterating on
+            w.ib_valid = false;
+            return VGI_ESTALE;
+        }
+    }
+    *iters_out = iters;
+    *nact_out = nact;
+    return VGGP_OK;
+}
+
+// Eigenbasis of the preconditioner from the Gram matrices G1, G2 of this step, into d.Qt / d.lam0; *reused: the kept basis serves.
+// Everything the steps do is exact in expectation for ANY orthonormal Q_d and any positive
+// dP = 1 + rho p l1 l2 -- P~ = (Q1 (x) Q2) diag(dP) (Q1 (x) Q2)^T is then simply another SPD preconditioner with a known
+// determinant: log|Sigma~| = sum log dP + tr log(P~^-1/2 Sigma~ P~^-1/2), the exact traces are traces against P~^-1 -- so the
+// cold Jacobi solve of G1, G2 (1.7 ms at m_d = 128, 74 ms at m_d = 256 where the solver works in global memory: 70 % of that
+// step) runs only on the first step of a plan, every 64 steps, and when the PCG needed 4 iterations more than right after the
+// last solve; in between the kept basis is reused with the Rayleigh quotients l_i = q_i^T G q_i of the CURRENT Gram matrices.
+// A reused basis on which the PCG takes 12 iterations more than right after the last solve is given up inside the step
+// (vgi_pcg's stale_limit, vgi_retry_stale).  VGGP_ITER_COLD_BASIS=1: solve every step.
+static int vgi_basis(vggp_ctx* c, VgMasked& w, const VgIter& it, const double* G1, const double* G2, bool* reused, hipStream_t st) {
+    static const bool always = getenv("VGGP_ITER_COLD_BASIS") != nullptr;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const double* G[2] = {G1, G2};
+    int rc;
+    // (not for RBF factors: rho lam1 lam2 spans eight decades there, and a basis that is 1e-2 off leaves P~^-1 Sigma~ with a
+    //  condition number of 1e4 -- the PCG stalls; measured.  Matern spectra are flat enough: 8 -> 11 -> 13 iterations over 4 % drift)
+    *reused = !always && w.ib_valid && w.ib_age < 64 && w.ib_last_its <= w.ib_ref_its + 4 && d1.kind != VGGP_KIND_RBF &&
+              d2.kind != VGGP_KIND_RBF;
+    if (*reused) {
+        double* Qk[2] = {it.Qk1, it.Qk2};
+        for (int k = 0; k < 2; ++k) {
+            VgDim& d = c->d[k];
+            VG_HIP(hipMemcpyAsync(d.Qt, Qk[k], sizeof(double) * d.m * d.m, hipMemcpyDeviceToDevice, st));
+            if ((rc = gemm1(d.Qt, d.m, 1, G[k], d.m, 1, it.Tq, d.m, d.m, d.m, d.m, st))) return rc;         // Q^T-rows times G
+            VGM_LAUNCH1D(vgi_rowdot_kernel, d.m, st, it.Tq, d.Qt, d.m, d.lam0);
+        }
+        ++w.ib_age;
+        w.ib_fresh = false;
+    } else {
+        VgEigJob ej[2];
+        for (int k = 0; k < 2; ++k) {
+            VgDim& d = c->d[k];
+            ej[k] = VgEigJob{G[k], d.lam0, d.Qt, nullptr, d.gwork, d.rotlog, d.roundlog, d.counters, d.m, d.max_rounds,
+                             (long)vg_eigh_log_bytes(d.m), 0};
+            ej[k].perm = d.perm;
+            ej[k].err = d.status + 1;
+        }
+        VG_HIP(vg_eigh_launch(ej, 2, st));
+        VG_HIP(hipMemcpyAsync(it.Qk1, d1.Qt, sizeof(double) * d1.m * d1.m, hipMemcpyDeviceToDevice, st));
+        VG_HIP(hipMemcpyAsync(it.Qk2, d2.Qt, sizeof(double) * d2.m * d2.m, hipMemcpyDeviceToDevice, st));
+        w.ib_valid = false;            // ... until this step has returned without an error
+        w.ib_fresh = true;
+    }
+    return VGGP_OK;
+}
+// ... and its book-keeping at the end of a step that returned without an error
+static void vgi_basis_done(VgMasked& w, int iters) {
+    if (w.ib_fresh) { w.ib_valid = true; w.ib_age = 0; w.ib_ref_its = iters; }
+    w.ib_last_its = iters;
+}
+// a step that gave its kept basis up (VGI_ESTALE) runs once more, now with a cold solve
+template <class Once>
+static int vgi_retry_stale(const char* fn, Once&& once) {
+    int rc = once();
+    if (rc == VGI_ESTALE) rc = once();
+    if (rc == VGI_ESTALE) { vg_set_error("%s: internal (stale basis after a cold solve)", fn); rc = VGGP_ESTATE; }
     return rc;
 }
+
+// right-hand sides (column 0 = c0, columns 1.. = z = P^1/2 z0;  Wz = P^-1 z = P^-1/2 z0) and the block solve Sigma~ X = R
+static int vgi_step_solve(vggp_ctx* c, VgMasked& w, const VgIter& it, const char* fn, double* C0, double p, double tol, int max_iter,
+                          bool reused, int* iters, hipStream_t st) {
+    const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
+    int rc, nact = 0;
+    VGM_LAUNCH1D(vgi_probe_kernel, w.M * nbc, st, it.X, m1, nbc, m2, 0x5647475000000001ULL);
+    if ((rc = vgi_rot(c, w, it, it.X, it.R, 1, 1, p, st))) return rc;
+    if ((rc = vgi_rot(c, w, it, it.X, it.Wz, 2, 1, p, st))) return rc;
+    VGM_LAUNCH1D(vgi_col_kernel, w.M, st, it.R, C0, m1, nbc, m2, 0, 0);
+    if ((rc = vgi_pcg(c, w, it, p, tol, max_iter, /*history=*/true, /*field2=*/false, reused ? w.ib_ref_its + 12 : 0, iters, &nact, st))) return rc;
+    if (nact > 0) { vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left)", fn, tol, max_iter, nact); return VGGP_ENOCONV; }
+    return VGGP_OK;
+}
+// log det: ts[0] = log|P|, ts[1] = the sum of the probes' quadratures
+static int vgi_logdet(vggp_ctx* c, VgMasked& w, const VgIter& it, double p, hipStream_t st) {
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    VG_HIP(hipMemsetAsync(it.ts, 0, VGI_NTS * sizeof(double), st));
+    VG_HIP(hipMemsetAsync(w.cholstatus, 0, sizeof(int), st));
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, w.m1, w.m2, (const double*)nullptr,
+                       (const double*)nullptr, (const double*)nullptr, 1, it.ts + 0);
+    hipLaunchKernelGGL(vgi_slq_kernel, dim3(1), dim3(64), 0, st, it.alh, it.beh, it.col, it.nbc, (double)w.M, it.pc, w.cholstatus);
+    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.pc, it.nbc - 1, it.ts + 1, 0);
+    return VGGP_OK;
+}
+// stochastic parts of the traces: fields of dU and of Wz with (B1,B2), (V1,B2), (B1,V2).  field(L, V, R, F): F = the field l^T V r of
+// the data kind; fsum(Fa, Fb, out): out = the sum of Fa Fb over the probe columns and the observations
+template <class Field, class FSum>
+static int vgi_field_terms(vggp_ctx* c, const VgMasked& w, const VgIter& it, const double* dU, Field&& field, FSum&& fsum) {
+    const double *B1 = c->d[0].BV, *V1 = B1 + (long)w.m1 * w.n1, *B2 = c->d[1].BV, *V2 = B2 + (long)w.m2 * (w.scattered ? w.n1 : w.n2);
+    int rc;
+    if ((rc = field(B1, it.Wz, B2, it.F0))) return rc;              // F0 = Fw^BB
+    if ((rc = field(B1, dU, B2, it.F1))) return rc;                 // F1 = Fu^BB
+    fsum(it.F1, it.F0, it.ts + 3);
+    if ((rc = field(V1, dU, B2, it.F2))) return rc;                 // Fu^VB
+    fsum(it.F2, it.F0, it.ts + 6);                                  // (u-w)^T Phi'_1^T w
+    if ((rc = field(B1, dU, V2, it.F2))) return rc;                 // Fu^BV
+    fsum(it.F2, it.F0, it.ts + 9);
+    if ((rc = field(V1, it.Wz, B2, it.F0))) return rc;              // Fw^VB
+    fsum(it.F1, it.F0, it.ts + 5);
+    if ((rc = field(B1, it.Wz, V2, it.F0))) return rc;              // Fw^BV
+    fsum(it.F1, it.F0, it.ts + 8);
+    return VGGP_OK;
+}
+// Mk terms: ts[11] = <dU, Mk1 Wz>, ts[13] = <dU, Wz Mk2^T> over the probe columns
+static int vgi_mk_terms(vggp_ctx* c, const VgMasked& w, const VgIter& it, const double* dU, hipStream_t st) {
+    const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    int rc;
+    if ((rc = gemm1(d1.Mk, m1, 1, it.Wz, (long)nbc * m2, 1, it.Tm, nbc * m2, m1, nbc * m2, m1, st))) return rc;
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, m1, nbc, m2,
+                       it.pc, (double*)nullptr);
+    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.pc, nbc, it.ts + 11, 1);
+    if ((rc = gemm1(it.Wz, m2, 1, d2.Mk, 1, m2, it.Tm, m2, m1 * nbc, m2, m2, st))) return rc;
+    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, m1, nbc, m2,
+                       it.pc, (double*)nullptr);
+    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.pc, nbc, it.ts + 13, 1);
+    return VGGP_OK;
+}
+// exact parts: the factors rotated into the eigenbasis of P (Rr_d = Q_d^T B_d, Rv_d = Q_d^T V_d) and their products RR_d = Rr_d o Rr_d,
+// RRV_d = Rr_d o Rv_d
+static int vgi_rotate_factors(vggp_ctx* c, const VgMasked& w, const VgIter& it, hipStream_t st) {
+    const int m1 = w.m1, m2 = w.m2;
+    const long n1 = w.n1, n2 = w.scattered ? w.n1 : w.n2;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const double *B1 = d1.BV, *V1 = B1 + m1 * n1, *B2 = d2.BV, *V2 = B2 + m2 * n2;
+    int rc;
+    if ((rc = gemm1(d1.Qt, m1, 1, B1, n1, 1, it.Rr1, (int)n1, m1, (int)n1, m1, st))) return rc;
+    if ((rc = gemm1(d1.Qt, m1, 1, V1, n1, 1, it.Rv1, (int)n1, m1, (int)n1, m1, st))) return rc;
+    if ((rc = gemm1(d2.Qt, m2, 1, B2, n2, 1, it.Rr2, (int)n2, m2, (int)n2, m2, st))) return rc;
+    if ((rc = gemm1(d2.Qt, m2, 1, V2, n2, 1, it.Rv2, (int)n2, m2, (int)n2, m2, st))) return rc;
+    VGM_LAUNCH1D(vgi_mul_kernel, m1 * n1, st, it.Rr1, it.Rr1, m1 * n1, it.RR1);
+    VGM_LAUNCH1D(vgi_mul_kernel, m1 * n1, st, it.Rr1, it.Rv1, m1 * n1, it.RRV1);
+    VGM_LAUNCH1D(vgi_mul_kernel, m2 * n2, st, it.Rr2, it.Rr2, m2 * n2, it.RR2);
+    VGM_LAUNCH1D(vgi_mul_kernel, m2 * n2, st, it.Rr2, it.Rv2, m2 * n2, it.RRV2);
+    return VGGP_OK;
+}
+// out[0] = sum (1 / dP) o Ex for the m1 x m2 product the data kind has left in it.Ex
+static void vgi_exact_sum(vggp_ctx* c, const VgMasked& w, const VgIter& it, double p, double* out, hipStream_t st) {
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, c->d[0].lam0, c->d[1].lam0, c->theta, p, w.m1, w.m2, it.Ex,
+                       (const double*)nullptr, (const double*)nullptr, 0, out);
+}
+// ts[10] = tr(P^-1 (Mk1 (x) I)) = sum_ab diag(Q1^T Mk1 Q1)_a / dP_ab, ts[12]: likewise dimension 2
+static int vgi_mk_traces(vggp_ctx* c, const VgMasked& w, const VgIter& it, double p, hipStream_t st) {
+    const int m1 = w.m1, m2 = w.m2;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    int rc;
+    if ((rc = gemm1(d1.Qt, m1, 1, d1.Mk, m1, 1, it.Tq, m1, m1, m1, m1, st))) return rc;
+    VGM_LAUNCH1D(vgi_rowdot_kernel, m1, st, it.Tq, d1.Qt, m1, it.dg1);
+    if ((rc = gemm1(d2.Qt, m2, 1, d2.Mk, m2, 1, it.Tq, m2, m2, m2, m2, st))) return rc;
+    VGM_LAUNCH1D(vgi_rowdot_kernel, m2, st, it.Tq, d2.Qt, m2, it.dg2);
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, m1, m2, (const double*)nullptr, it.dg1,
+                       (const double*)nullptr, 0, it.ts + 10);
+    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, m1, m2, (const double*)nullptr,
+                       (const double*)nullptr, it.dg2, 0, it.ts + 12);
+    return VGGP_OK;
+}
+// The dense step's reductions that do not involve Sigma~^-1 as a matrix (the six that do come from the combine kernel): the ones both
+// data kinds share.  The drivers add RJ_TRPHI, RJ_Z1, RJ_HV1, RJ_Z2, RJ_HV2 over their observations.
+static void vgi_red_job(VgmRedArgs& ra, int k, const double* a, const double* b, long n, long sa, long sb, int op, const double* cc = nullptr) {
+    ra.job[k] = VgmRedJob{a, b, cc, n, sa, sb, op};
+}
+static void vgi_red_jobs(vggp_ctx* c, const VgMasked& w, const double* C0, VgmRedArgs& ra) {
+    const long m1 = w.m1, m2 = w.m2, M = w.M;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const double *C1 = C0 + M, *C2 = C1 + M;
+    ra.njobs = RJ_COUNT;
+    ra.partial = w.partial;
+    for (int k = 0; k < RJ_COUNT; ++k) vgi_red_job(ra, k, w.a0, w.a0, 0, 1, 1, 0);
+    vgi_red_job(ra, RJ_Q, C0, w.a0, M, 1, 1, 0);
+    vgi_red_job(ra, RJ_AA, w.a0, w.a0, M, 1, 1, 0);
+    vgi_red_job(ra, RJ_TRMK1, d1.Mk, nullptr, m1, m1 + 1, 0, 2);
+    vgi_red_job(ra, RJ_AC1, w.a0, C1, M, 1, 1, 0);
+    vgi_red_job(ra, RJ_MKA1, w.MkA1, w.a0, M, 1, 1, 0);
+    vgi_red_job(ra, RJ_MK1PT, d1.Mk, w.PT1, m1 * m1, 1, 1, 0);
+    vgi_red_job(ra, RJ_TRMK2, d2.Mk, nullptr, m2, m2 + 1, 0, 2);
+    vgi_red_job(ra, RJ_AC2, w.a0, C2, M, 1, 1, 0);
+    vgi_red_job(ra, RJ_MKA2, w.MkA2, w.a0, M, 1, 1, 0);
+    vgi_red_job(ra, RJ_MK2PT, d2.Mk, w.PT2, m2 * m2, 1, 1, 0);
+}
+// reductions, combine, final, copy-back and the status of the step (`what`: "masked" / "scattered", n observations with sum of squares yy)
+static int vgi_finish(vggp_ctx* c, VgMasked& w, const VgIter& it, const char* what, const VgmRedArgs& ra, double n, double yy, int iters,
+                      double* elbo_out, double grad_out[5], vggp_info* info, hipStream_t st) {
+    const int n_probes = it.nbc - 1;
+    hipLaunchKernelGGL(vgm_red_kernel, dim3(VG_MD_NPART, RJ_COUNT), dim3(256), 0, st, ra);
+    hipLaunchKernelGGL(vgm_sum_kernel, dim3(1), dim3(64), 0, st, w.partial, w.scal, 0u, 1);
+    hipLaunchKernelGGL(vgi_combine_kernel, dim3(1), dim3(64), 0, st, it.ts, c->theta, (double)w.M, n_probes, w.scal);
+    VgmFinalArgs fa{c->theta, w.scal, w.out, n, yy, w.m1, w.m2};
+    hipLaunchKernelGGL(vgm_final_kernel, dim3(1), dim3(64), 0, st, fa);
+    VG_HIP(hipGetLastError());
+    VG_HIP(hipMemcpyAsync(c->h_out->out, w.out, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
+    for (int k = 0; k < 2; ++k) {
+        VG_HIP(hipMemcpyAsync(&c->h_out->jitter[k], c->d[k].jitter, sizeof(double), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipMemcpyAsync(&c->h_out->status[k], c->d[k].status, sizeof(int), hipMemcpyDeviceToHost, st));
+        VG_HIP(hipMemcpyAsync(&c->h_out->counters[k][2], c->d[k].counters + 2, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    VG_HIP(hipMemcpyAsync(&c->h_out->counters[1][3], w.cholstatus, sizeof(int), hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));
+    *elbo_out = c->h_out->out[0];
+    for (int i = 0; i < 5; ++i) grad_out[i] = c->h_out->out[1 + i];
+    int status = c->h_out->status[0] ? c->h_out->status[0] : (c->h_out->status[1] ? c->h_out->status[1] : 0);
+    if (!status) status = c->h_out->counters[0][2] ? c->h_out->counters[0][2] : c->h_out->counters[1][2];
+    if (info) {
+        info->jitter1 = c->h_out->jitter[0]; info->jitter2 = c->h_out->jitter[1];
+        info->sweeps1 = n_probes; info->sweeps2 = 0; info->rounds1 = iters; info->rounds2 = 0;
+        info->status = status; info->polished = 0;
+    }
+    if (status == VGGP_ENOTPD) { vg_set_error("iterative %s step: a factor is not positive definite", what); return VGGP_ENOTPD; }
+    if (status) { vg_set_error("iterative %s step: the preconditioner's eigensolver failed (status %d)", what, status); return VGGP_ENOCONV; }
+    if (c->h_out->counters[1][3]) { vg_set_error("iterative %s step: the Lanczos quadrature failed (code %d)", what, c->h_out->counters[1][3]); return VGGP_ENOCONV; }
+    vgi_basis_done(w, iters);
+    c->have_step = false; c->have_partials = false;
+    c->have_iter = true;             // a0, the factors and the preconditioner's basis are there for the iterative read-outs
+    return VGGP_OK;
+}
+
+// ---- the masked step -------------------------------------------------------------------------------------------------------------------
 static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs, const double theta[5],
                             int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream) {
+    static const char* fn = "vggp_elbo_step_masked_iter";
     if (!c || !c->planned) { vg_set_error("vggp_elbo_step_masked_iter: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(Ym && W && theta && elbo_out && grad_out, "vggp_elbo_step_masked_iter: null argument");
     c->have_masked = false;
@@ -1418,217 +1685,61 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     if (rc) return rc;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
     VgIter it;
-    if ((rc = vgi_prepare(c, w, it, nbc, max_iter))) return rc;
+    if ((rc = vgi_prepare(w, it, nbc, max_iter))) return rc;
     // factors, Cholesky, B|V, Mk, the projections C0, C1, C2 and the full-grid Gram matrices G1 (d1.GH), G2 (mpay)
     if ((rc = vg_partials_enqueue(c, Ym, w.mpay, st))) return rc;
-    VgDim &d1 = c->d[0], &d2 = c->d[1];
-    const double *B1 = d1.BV, *V1 = d1.BV + m1 * n1, *B2 = d2.BV, *V2 = d2.BV + m2 * n2;
-    double *C0 = w.mpay + 2 * m2 * m2, *C1 = C0 + M, *C2 = C1 + M;
+    double* C0 = w.mpay + 2 * m2 * m2;
     if ((rc = vgm_colstats(c, w, W, st))) return rc;
     hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
     bool reused = false;
-    // Eigenbasis of the preconditioner.  Everything below is exact in expectation for ANY orthonormal Q_d and any positive
-    // dP = 1 + rho p l1 l2 -- P~ = (Q1 (x) Q2) diag(dP) (Q1 (x) Q2)^T is then simply another SPD preconditioner with a known
-    // determinant: log|Sigma~| = sum log dP + tr log(P~^-1/2 Sigma~ P~^-1/2), the exact traces are traces against P~^-1 -- so the
-    // cold Jacobi solve of G1, G2 (1.7 ms at m_d = 128, 74 ms at m_d = 256 where the solver works in global memory: 70 % of that
-    // step) runs only on the first step of a plan, every 64 steps, and when the PCG needed 4 iterations more than right after the
-    // last solve; in between the kept basis is reused with the Rayleigh quotients l_i = q_i^T G q_i of the CURRENT Gram matrices.
-    // VGGP_ITER_COLD_BASIS=1: solve every step.
-    {
-        static const bool always = getenv("VGGP_ITER_COLD_BASIS") != nullptr;
-        const double* G[2] = {d1.GH, w.mpay};
-        // (not for RBF factors: rho lam1 lam2 spans eight decades there, and a basis that is 1e-2 off leaves P~^-1 Sigma~ with a
-        //  condition number of 1e4 -- the PCG stalls; measured.  Matern spectra are flat enough: 8 -> 11 -> 13 iterations over 4 % drift)
-        const bool reuse = !always && w.ib_valid && w.ib_age < 64 && w.ib_last_its <= w.ib_ref_its + 4 && d1.kind != VGGP_KIND_RBF &&
-                           d2.kind != VGGP_KIND_RBF;
-        reused = reuse;
-        if (reuse) {
-            double* Qk[2] = {it.Qk1, it.Qk2};
-            for (int k = 0; k < 2; ++k) {
-                VgDim& d = c->d[k];
-                VG_HIP(hipMemcpyAsync(d.Qt, Qk[k], sizeof(double) * d.m * d.m, hipMemcpyDeviceToDevice, st));
-                if ((rc = gemm1(d.Qt, d.m, 1, G[k], d.m, 1, it.Tq, d.m, d.m, d.m, d.m, st))) return rc;         // Q^T-rows times G
-                VGM_LAUNCH1D(vgi_rowdot_kernel, d.m, st, it.Tq, d.Qt, d.m, d.lam0);
-            }
-            ++w.ib_age;
-            w.ib_fresh = false;
-        } else {
-            VgEigJob ej[2];
-            for (int k = 0; k < 2; ++k) {
-                VgDim& d = c->d[k];
-                ej[k] = VgEigJob{G[k], d.lam0, d.Qt, nullptr, d.gwork, d.rotlog, d.roundlog, d.counters, d.m, d.max_rounds,
-                                 (long)vg_eigh_log_bytes(d.m), 0};
-                ej[k].perm = d.perm;
-                ej[k].err = d.status + 1;
-            }
-            VG_HIP(vg_eigh_launch(ej, 2, st));
-            VG_HIP(hipMemcpyAsync(it.Qk1, d1.Qt, sizeof(double) * m1 * m1, hipMemcpyDeviceToDevice, st));
-            VG_HIP(hipMemcpyAsync(it.Qk2, d2.Qt, sizeof(double) * m2 * m2, hipMemcpyDeviceToDevice, st));
-            w.ib_valid = false;            // ... until this step has returned without an error
-            w.ib_fresh = true;
-        }
-    }
+    if ((rc = vgi_basis(c, w, it, c->d[0].GH, w.mpay, &reused, st))) return rc;
     const double p = n_obs / ((double)n1 * (double)n2);
-    const long nb = M * nbc;
-    // right-hand sides: column 0 = c0, columns 1.. = z = P^1/2 z0;  Wz = P^-1 z = P^-1/2 z0
-    VGM_LAUNCH1D(vgi_probe_kernel, nb, st, it.X, (int)m1, nbc, (int)m2, 0x5647475000000001ULL);
-    if ((rc = vgi_rot(c, w, it, it.X, it.R, 1, 1, p, st))) return rc;
-    if ((rc = vgi_rot(c, w, it, it.X, it.Wz, 2, 1, p, st))) return rc;
-    VGM_LAUNCH1D(vgi_col_kernel, M, st, it.R, C0, (int)m1, nbc, (int)m2, 0, 0);
-    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
-    // PCG
-    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col, it.col + 3 * nbc);
-    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
-    int iters = 0, nact = nbc;
-    for (int k = 0; k < max_iter && nact > 0; ++k) {
-        // AP = Pd + rho B1 (Wt o (B1^T Pd B2)) B2^T
-        if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
-        VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
-        if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
-        VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                           (int)m2, it.col + nbc, (double*)nullptr);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, k, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 1);
-        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col + 5 * nbc,
-                           it.col + 3 * nbc);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, k, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 2);
-        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipStreamSynchronize(st));
-        nact = c->h_out->counters[0][0];
-        iters = k + 1;
-        if (reused && nact > 0 && iters > w.ib_ref_its + 12) {      // the kept basis has drifted too far: not worth iterating on
-            w.ib_valid = false;
-            return VGI_ESTALE;
-        }
-    }
-    if (nact > 0) { vg_set_error("vggp_elbo_step_masked_iter: PCG did not reach %.1e in %d iterations (%d columns left)", tol, max_iter, nact); return VGGP_ENOCONV; }
-    // log det: log|P| + the quadratures
-    VG_HIP(hipMemsetAsync(it.ts, 0, 64 * sizeof(double), st));
-    VG_HIP(hipMemsetAsync(w.cholstatus, 0, sizeof(int), st));
-    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr,
-                       (const double*)nullptr, (const double*)nullptr, 1, it.ts + 0);
-    hipLaunchKernelGGL(vgi_slq_kernel, dim3(1), dim3(64), 0, st, it.alh, it.beh, it.col, nbc, (double)M, it.ts + 32, w.cholstatus);
-    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.ts + 32, n_probes, it.ts + 1, 0);
+    int iters = 0;
+    if ((rc = vgi_step_solve(c, w, it, fn, C0, p, tol, max_iter, reused, &iters, st))) return rc;
+    if ((rc = vgi_logdet(c, w, it, p, st))) return rc;
     // a0 and the a0 terms of the gradient
     VGM_LAUNCH1D(vgi_col_kernel, M, st, it.X, w.a0, (int)m1, nbc, (int)m2, 0, 1);
     if ((rc = vgm_a0_terms(c, w, st))) return rc;
-    // dU = Sigma~^-1 z - P^-1 z (probe columns)
-    VGM_LAUNCH1D(vgi_sub_kernel, nb, st, it.X, it.Wz, nb, it.Zp);
-    double* dU = it.Zp;
-    // stochastic parts of the traces: fields of dU and of Wz with (B1,B2), (V1,B2), (B1,V2)
+    // dU = Sigma~^-1 z - P^-1 z (probe columns); the control variates' fields are weighted by the mask
+    VGM_LAUNCH1D(vgi_sub_kernel, M * nbc, st, it.X, it.Wz, M * nbc, it.Zp);
+    const double* dU = it.Zp;
+    auto field = [&](const double* L, const double* V, const double* R, double* F) { return vgi_field(w, it, L, V, R, F, st); };
     auto fsum = [&](const double* Fa, const double* Fb, double* out) {
         hipLaunchKernelGGL(vgi_fieldsum_part_kernel, dim3(1024), dim3(256), 0, st, Fa, Fb, it.Wt, n1, nbc, n2, it.fpart);
         hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.fpart, 1024, out, 0);
     };
-    if ((rc = vgi_field(w, it, B1, it.Wz, B2, it.F0, st))) return rc;              // F0 = Fw^BB
-    if ((rc = vgi_field(w, it, B1, dU, B2, it.F1, st))) return rc;                 // F1 = Fu^BB
-    fsum(it.F1, it.F0, it.ts + 3);
-    if ((rc = vgi_field(w, it, V1, dU, B2, it.F2, st))) return rc;                 // Fu^VB
-    fsum(it.F2, it.F0, it.ts + 6);                                                 // (u-w)^T Phi'_1^T w
-    if ((rc = vgi_field(w, it, B1, dU, V2, it.F2, st))) return rc;                 // Fu^BV
-    fsum(it.F2, it.F0, it.ts + 9);
-    if ((rc = vgi_field(w, it, V1, it.Wz, B2, it.F0, st))) return rc;              // Fw^VB
-    fsum(it.F1, it.F0, it.ts + 5);
-    if ((rc = vgi_field(w, it, B1, it.Wz, V2, it.F0, st))) return rc;              // Fw^BV
-    fsum(it.F1, it.F0, it.ts + 8);
-    // Mk terms: <dU, Mk1 Wz>, <dU, Wz Mk2^T>
-    if ((rc = gemm1(d1.Mk, m1, 1, it.Wz, (long)nbc * m2, 1, it.Tm, nbc * (int)m2, (int)m1, nbc * (int)m2, (int)m1, st))) return rc;
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                       (int)m2, it.ts + 32, (double*)nullptr);
-    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.ts + 32, nbc, it.ts + 11, 1);
-    if ((rc = gemm1(it.Wz, m2, 1, d2.Mk, 1, m2, it.Tm, (int)m2, (int)(m1 * nbc), (int)m2, (int)m2, st))) return rc;
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                       (int)m2, it.ts + 32, (double*)nullptr);
-    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.ts + 32, nbc, it.ts + 13, 1);
-    // exact parts: factors rotated into the eigenbasis of P
-    if ((rc = gemm1(d1.Qt, m1, 1, B1, n1, 1, it.Rr1, (int)n1, (int)m1, (int)n1, (int)m1, st))) return rc;
-    if ((rc = gemm1(d1.Qt, m1, 1, V1, n1, 1, it.Rv1, (int)n1, (int)m1, (int)n1, (int)m1, st))) return rc;
-    if ((rc = gemm1(d2.Qt, m2, 1, B2, n2, 1, it.Rr2, (int)n2, (int)m2, (int)n2, (int)m2, st))) return rc;
-    if ((rc = gemm1(d2.Qt, m2, 1, V2, n2, 1, it.Rv2, (int)n2, (int)m2, (int)n2, (int)m2, st))) return rc;
-    VGM_LAUNCH1D(vgi_mul_kernel, m1 * n1, st, it.Rr1, it.Rr1, m1 * n1, it.RR1);
-    VGM_LAUNCH1D(vgi_mul_kernel, m1 * n1, st, it.Rr1, it.Rv1, m1 * n1, it.RRV1);
-    VGM_LAUNCH1D(vgi_mul_kernel, m2 * n2, st, it.Rr2, it.Rr2, m2 * n2, it.RR2);
-    VGM_LAUNCH1D(vgi_mul_kernel, m2 * n2, st, it.Rr2, it.Rv2, m2 * n2, it.RRV2);
-    if ((rc = gemm1(it.Wt, n2, 1, it.RR2, 1, n2, it.TW, (int)m2, (int)n1, (int)m2, (int)n2, st))) return rc;        // Wt RR2^T  (n1 x m2)
+    if ((rc = vgi_field_terms(c, w, it, dU, field, fsum))) return rc;
+    if ((rc = vgi_mk_terms(c, w, it, dU, st))) return rc;
+    // exact parts tr(P^-1 Phi(.)): the mask enters through TW = Wt RR2^T (n1 x m2), then one m1 x m2 product over the n1 rows each
+    if ((rc = vgi_rotate_factors(c, w, it, st))) return rc;
+    if ((rc = gemm1(it.Wt, n2, 1, it.RR2, 1, n2, it.TW, (int)m2, (int)n1, (int)m2, (int)n2, st))) return rc;
     if ((rc = gemm1(it.Wt, n2, 1, it.RRV2, 1, n2, it.TWv, (int)m2, (int)n1, (int)m2, (int)n2, st))) return rc;
     auto exact = [&](const double* RRa, const double* TWb, double* out) -> int {
         int r2 = gemm_longk(RRa, n1, 1, TWb, m2, 1, it.Ex, (int)m1, (int)m2, (int)n1, w.T, st);
         if (r2) return r2;
-        hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, it.Ex,
-                           (const double*)nullptr, (const double*)nullptr, 0, out);
+        vgi_exact_sum(c, w, it, p, out, st);
         return VGGP_OK;
     };
     if ((rc = exact(it.RR1, it.TW, it.ts + 2))) return rc;
     if ((rc = exact(it.RRV1, it.TW, it.ts + 4))) return rc;
     if ((rc = exact(it.RR1, it.TWv, it.ts + 7))) return rc;
-    // tr(P^-1 (Mk1 (x) I)) = sum_ab diag(Q1^T Mk1 Q1)_a / dP_ab, likewise dimension 2
-    if ((rc = gemm1(d1.Qt, m1, 1, d1.Mk, m1, 1, it.Tq, (int)m1, (int)m1, (int)m1, (int)m1, st))) return rc;
-    VGM_LAUNCH1D(vgi_rowdot_kernel, m1, st, it.Tq, d1.Qt, (int)m1, it.dg1);
-    if ((rc = gemm1(d2.Qt, m2, 1, d2.Mk, m2, 1, it.Tq, (int)m2, (int)m2, (int)m2, (int)m2, st))) return rc;
-    VGM_LAUNCH1D(vgi_rowdot_kernel, m2, st, it.Tq, d2.Qt, (int)m2, it.dg2);
-    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr, it.dg1,
-                       (const double*)nullptr, 0, it.ts + 10);
-    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr,
-                       (const double*)nullptr, it.dg2, 0, it.ts + 12);
-    // the dense step's reductions that do not involve Sigma~^-1 as a matrix; the six that do come from the combine kernel
+    if ((rc = vgi_mk_traces(c, w, it, p, st))) return rc;
     VgmRedArgs ra;
-    ra.njobs = RJ_COUNT;
-    ra.partial = w.partial;
-    auto job = [&](int k, const double* a, const double* b, long n, long sa, long sb, int op, const double* cc = nullptr) {
-        ra.job[k] = VgmRedJob{a, b, cc, n, sa, sb, op};
-    };
-    for (int k = 0; k < RJ_COUNT; ++k) job(k, w.a0, w.a0, 0, 1, 1, 0);
-    job(RJ_Q, C0, w.a0, M, 1, 1, 0);
-    job(RJ_AA, w.a0, w.a0, M, 1, 1, 0);
-    job(RJ_TRPHI, w.nb1, w.wn2, n1, 1, 1, 0);
-    job(RJ_TRMK1, d1.Mk, nullptr, m1, m1 + 1, 0, 2);
-    job(RJ_AC1, w.a0, C1, M, 1, 1, 0);
-    job(RJ_MKA1, w.MkA1, w.a0, M, 1, 1, 0);
-    job(RJ_Z1, W, w.Zb, n1 * n2, 1, 1, 3, w.Zv1);
-    job(RJ_HV1, w.hv1, w.wn2, n1, 1, 1, 0);
-    job(RJ_MK1PT, d1.Mk, w.PT1, m1 * m1, 1, 1, 0);
-    job(RJ_TRMK2, d2.Mk, nullptr, m2, m2 + 1, 0, 2);
-    job(RJ_AC2, w.a0, C2, M, 1, 1, 0);
-    job(RJ_MKA2, w.MkA2, w.a0, M, 1, 1, 0);
-    job(RJ_Z2, W, w.Zb, n1 * n2, 1, 1, 3, w.Zv2);
-    job(RJ_HV2, w.hv2, w.wn1, n2, 1, 1, 0);
-    job(RJ_MK2PT, d2.Mk, w.PT2, m2 * m2, 1, 1, 0);
-    hipLaunchKernelGGL(vgm_red_kernel, dim3(VG_MD_NPART, RJ_COUNT), dim3(256), 0, st, ra);
-    hipLaunchKernelGGL(vgm_sum_kernel, dim3(1), dim3(64), 0, st, w.partial, w.scal, 0u, 1);
-    hipLaunchKernelGGL(vgi_combine_kernel, dim3(1), dim3(64), 0, st, it.ts, c->theta, (double)M, n_probes, w.scal);
-    VgmFinalArgs fa{c->theta, w.scal, w.out, n_obs, yy_obs, (int)m1, (int)m2};
-    hipLaunchKernelGGL(vgm_final_kernel, dim3(1), dim3(64), 0, st, fa);
-    VG_HIP(hipGetLastError());
-    VG_HIP(hipMemcpyAsync(c->h_out->out, w.out, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-    for (int k = 0; k < 2; ++k) {
-        VG_HIP(hipMemcpyAsync(&c->h_out->jitter[k], c->d[k].jitter, sizeof(double), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipMemcpyAsync(&c->h_out->status[k], c->d[k].status, sizeof(int), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipMemcpyAsync(&c->h_out->counters[k][2], c->d[k].counters + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    VG_HIP(hipMemcpyAsync(&c->h_out->counters[1][3], w.cholstatus, sizeof(int), hipMemcpyDeviceToHost, st));
-    VG_HIP(hipStreamSynchronize(st));
-    *elbo_out = c->h_out->out[0];
-    for (int i = 0; i < 5; ++i) grad_out[i] = c->h_out->out[1 + i];
-    int status = c->h_out->status[0] ? c->h_out->status[0] : (c->h_out->status[1] ? c->h_out->status[1] : 0);
-    if (!status) status = c->h_out->counters[0][2] ? c->h_out->counters[0][2] : c->h_out->counters[1][2];
-    if (info) {
-        info->jitter1 = c->h_out->jitter[0]; info->jitter2 = c->h_out->jitter[1];
-        info->sweeps1 = n_probes; info->sweeps2 = 0; info->rounds1 = iters; info->rounds2 = 0;
-        info->status = status; info->polished = 0;
-    }
-    if (status == VGGP_ENOTPD) { vg_set_error("iterative masked step: a factor is not positive definite"); return VGGP_ENOTPD; }
-    if (status) { vg_set_error("iterative masked step: the preconditioner's eigensolver failed (status %d)", status); return VGGP_ENOCONV; }
-    if (c->h_out->counters[1][3]) { vg_set_error("iterative masked step: the Lanczos quadrature failed (code %d)", c->h_out->counters[1][3]); return VGGP_ENOCONV; }
-    if (w.ib_fresh) { w.ib_valid = true; w.ib_age = 0; w.ib_ref_its = iters; }
-    w.ib_last_its = iters;
-    c->have_step = false; c->have_partials = false;
-    c->have_iter = true;             // a0, the factors and the preconditioner's basis are there for the iterative read-outs
-    return VGGP_OK;
+    vgi_red_jobs(c, w, C0, ra);
+    vgi_red_job(ra, RJ_TRPHI, w.nb1, w.wn2, n1, 1, 1, 0);
+    vgi_red_job(ra, RJ_Z1, W, w.Zb, n1 * n2, 1, 1, 3, w.Zv1);
+    vgi_red_job(ra, RJ_HV1, w.hv1, w.wn2, n1, 1, 1, 0);
+    vgi_red_job(ra, RJ_Z2, W, w.Zb, n1 * n2, 1, 1, 3, w.Zv2);
+    vgi_red_job(ra, RJ_HV2, w.hv2, w.wn1, n2, 1, 1, 0);
+    return vgi_finish(c, w, it, "masked", ra, n_obs, yy_obs, iters, elbo_out, grad_out, info, st);
+}
+extern "C" int vggp_elbo_step_masked_iter(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs, const double theta[5],
+                                          int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5], vggp_info* info,
+                                          void* stream) {
+    VG_NOT_PAIRED(c, "vggp_elbo_step_masked_iter");
+    return vgi_retry_stale("vggp_elbo_step_masked_iter", [&] {
+        return masked_iter_once(c, Ym, W, n_obs, yy_obs, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
+    });
 }
 
 // ================================================================================================================================
@@ -1645,11 +1756,11 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
 // preconditioner basis Qk1/Qk2 in it, is not touched.  Specification: tests/masked_iter_readout_spec.py.
 // ================================================================================================================================
 struct VgReadout {
-    VgIter it;                  // the block vectors the step's helpers work on (Wz, alh, beh: one row each; the rest of VgIter unused)
+    VgIter it;                  // the block vectors the step's helpers work on (alh, beh: one row each; no Wz; the rest of VgIter unused)
+    double p;                   // the step's observed fraction (scattered: 1 / N)
     double *T;                  // the right-hand sides, kept for the reductions
     double *A1, *A2, *U1, *U2;  // posterior(x*): factor columns a_d(x*) and U_d = L0_d^-1 a_d  [m_d][cn]
     long long* cells;           // q(v): this block's flat cell indices
-    double* krs;                // scattered: split scratch of the back kernel
 };
 
 // T[a][c][b] = U1[a][c] U2[b][c] for the cn columns of this block (U_d: [m_d][cn]); the unused columns of a ragged block are zero
@@ -1701,96 +1812,117 @@ __global__ __launch_bounds__(256) void vgi_readout_reduce_kernel(const double* T
     }
 }
 
-static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post) {
-    const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M, mx = std::max(m1, m2);
-    size_t off = 0;
-    char* base = nullptr;
-    VgIter& it = r.it;
-    const bool sc = w.scattered;          // scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N]
-    for (int pass = 0; pass < 2; ++pass) {
-        off = 0;
-        auto take = [&](size_t count) {
-            off = (off + 255) & ~size_t(255);
-            double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-            off += count * sizeof(double);
-            return p;
-        };
-        it.Wt = take(sc ? 0 : n1 * n2);
-        it.X = take(M * nbc); it.R = take(M * nbc); it.Zp = take(M * nbc); it.Pd = take(M * nbc); it.AP = take(M * nbc);
-        it.Tm = take(M * nbc); it.Tm2 = take(M * nbc); r.T = take(M * nbc);
-        it.T1 = take(sc ? 0 : n1 * nbc * mx);
-        it.F0 = take(sc ? n1 * nbc : n1 * nbc * n2);
-        it.alh = take((size_t)nbc); it.beh = take((size_t)nbc);
-        it.col = take(8 * (size_t)nbc);
-        r.A1 = take(post ? m1 * nbc : 0); r.A2 = take(post ? m2 * nbc : 0);
-        r.U1 = take(post ? m1 * nbc : 0); r.U2 = take(post ? m2 * nbc : 0);
-        r.cells = reinterpret_cast<long long*>(take((size_t)nbc));
-        r.krs = take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
-        it.nact = reinterpret_cast<int*>(take(8));
-        if (pass == 0) {
-            const size_t need = off + 4096;
-            if (w.rbytes < need) {
-                if (w.rmem) { VG_HIP(hipFree(w.rmem)); w.rmem = nullptr; w.rbytes = 0; }
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-                    vg_set_error("the read-out workspace of the iterative step needs %.1f GiB at block = %d but only %.1f GiB of device "
-                                 "memory are free (a smaller block needs less)", (double)need / 1073741824.0, nbc, (double)free_b / 1073741824.0);
-                    return VGGP_ENOMEM;
-                }
-                VG_HIP(hipMalloc(&w.rmem, need));
-                w.rbytes = need;
-            }
-            base = reinterpret_cast<char*>(w.rmem);
-        }
-    }
-    it.nbc = nbc; it.maxit = 1;
+// the outputscale's exponent in q(v): -1 for the inter-domain bases (VFF, B1)
+static int vgi_scale_exp(const VgDim& d) { return (d.basis == VGGP_BASIS_VFF || d.basis == VGGP_BASIS_B1) ? -1 : 1; }
+// q(v) mean of every cell from the a0 an iterative step left: L0_1 A0 L0_2^T, scaled as vggp_qv_masked scales it (two GEMMs, no solve)
+static int vgi_qv_mean(vggp_ctx* c, VgMasked& w, double* mean, hipStream_t st) {
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const int m1 = w.m1, m2 = w.m2;
+    int rc;
+    if ((rc = gemm1(d1.L0, m1, 1, w.a0, m2, 1, w.MkA1, m2, m1, m2, m1, st))) return rc;
+    if ((rc = gemm1(w.MkA1, m2, 1, d2.L0, 1, m2, mean, m2, m1, m2, m2, st))) return rc;
+    VGM_LAUNCH1D(vgm_scale_rho_kernel, w.M, st, mean, w.M, c->theta, vgi_scale_exp(d1), vgi_scale_exp(d2));
+    VG_HIP(hipGetLastError());
+    return VGGP_OK;
+}
+// posterior(x*): factor columns A_d = a_d(x*_d) and U_d = L0_d^-1 A_d ([m_d][cn]) of cn points
+static int vgi_whitened_columns(vggp_ctx* c, const double* xs1, const double* xs2, int cn, double* A1, double* A2, double* U1, double* U2,
+                                hipStream_t st) {
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    VgFactorJob fj[2] = {VgFactorJob{xs1, d1.grid, A1, nullptr, nullptr, nullptr, cn, d1.m, d1.kind, d1.basis, 0, 0.0, c->desc.flags},
+                         VgFactorJob{xs2, d2.grid, A2, nullptr, nullptr, nullptr, cn, d2.m, d2.kind, d2.basis, 1, 0.0, c->desc.flags}};
+    VG_HIP(vg_factor_build_launch(fj, 2, c->theta, st));
+    VgGemmBatch g;
+    vg_gemm_init(&g);
+    vg_gemm_add(&g, d1.Linv0, d1.m, 1, A1, cn, 1, U1, cn, d1.m, cn, d1.m);
+    vg_gemm_add(&g, d2.Linv0, d2.m, 1, A2, cn, 1, U2, cn, d2.m, cn, d2.m);
+    VG_HIP(vg_gemm_launch(&g, st));
     return VGGP_OK;
 }
 
-// Sigma~ X = T for the block in r.T: the step's PCG loop without the coefficient history (zero columns start inactive).  A function of
-// (the step's operands, r.T) -> r.it.X for either data kind: the masked Kronecker operator, or the Khatri-Rao one with p = 1 / N
-static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, double tol, int max_iter, int* iters_out, int* nact_out,
-                             hipStream_t st) {
-    VgIter& it = r.it;
-    const long m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M;
-    const int nbc = it.nbc;
-    const long nb = M * nbc;
-    const double *B1 = c->d[0].BV, *B2 = c->d[1].BV;
-    int rc;
-    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
-    VG_HIP(hipMemcpyAsync(it.R, r.T, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col, it.col + 3 * nbc);
-    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
-    int iters = 0, nact = nbc;
-    for (int k = 0; k < max_iter && nact > 0; ++k) {
-        if (w.scattered) {               // the Khatri-Rao operator of the scattered step (n1 points); the field kernel in its two-column
-                                         // instantiation: the same bits at 2.2 x the rate, at 64 columns and at 16
-            VG_HIP(vg_kr_field2_launch(B1, B2, it.Pd, (int)m1, (int)m2, n1, nbc, it.F0, st));
-            VG_HIP(vg_kr_back_launch(B1, B2, it.F0, (int)m1, (int)m2, n1, nbc, it.AP, r.krs, st));
-        } else {
-            if ((rc = vgi_field(w, it, B1, it.Pd, B2, it.F0, st))) return rc;
-            VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
-            if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
-        }
-        VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                           (int)m2, it.col + nbc, (double*)nullptr);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, 0, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 1);
-        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col + 5 * nbc,
-                           it.col + 3 * nbc);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, 0, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 2);
-        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipStreamSynchronize(st));
-        nact = c->h_out->counters[0][0];
-        iters = k + 1;
+// What every read-out entry checks first: the context, the data kind of its plan (not_scattered / not_grid: the entry's own words for
+// a plan of the other kind), W and n_obs of a masked step (bad_W: likewise) and the width of a block solve
+static int vgi_readout_enter(vggp_ctx* c, const char* fn, bool scattered, const char* not_scattered, const char* not_grid, const char* bad_W,
+                             const double* W, double n_obs, int block) {
+    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
+    VG_NOT_PAIRED(c, fn);
+    if (scattered) VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: %s", fn, not_scattered);
+    else VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: %s", fn, not_grid);
+    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
+    if (!scattered) VG_REQUIRE(W && std::isfinite(n_obs) && n_obs > 0.0, "%s: %s", fn, bad_W);
+    VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
+    return VGGP_OK;
+}
+// ... and, once its own arguments are checked: the block width (0: the widest that fits), a finished iterative step, the defaults of
+// tol and max_iter, a zeroed info
+static int vgi_readout_defaults(vggp_ctx* c, const char* fn, bool scattered, int* block, double* tol, int* max_iter, vggp_info* info) {
+    const long n1 = c->desc.n1, n2 = c->desc.n2, M = (long)c->desc.m1 * c->desc.m2;
+    auto fits = [&](long b) {
+        return scattered ? (n1 * b < (1L << 31) && M * b < (1L << 31)) : (n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31));
+    };
+    if (*block <= 0) { *block = 64; while (*block > 1 && !fits(*block)) *block >>= 1; }
+    VG_REQUIRE(fits(*block), "%s: problem too large for block = %d", fn, *block);
+    if (!c->have_iter || !c->masked) {
+        vg_set_error("%s: no finished %s on this context", fn, scattered ? "vggp_elbo_step_scattered_iter" : "vggp_elbo_step_masked_iter");
+        return VGGP_ESTATE;
     }
-    *iters_out = iters;
-    *nact_out = nact;
+    if (*max_iter <= 0) *max_iter = 100;
+    if (!(*tol > 0.0)) *tol = 1e-10;
+    if (info) { info->jitter1 = info->jitter2 = 0.0; info->sweeps1 = info->sweeps2 = info->rounds1 = info->rounds2 = 0; info->status = 0; info->polished = 0; }
+    return VGGP_OK;
+}
+
+// The read-outs' arena (w.rmem) for blocks of nbc columns, the transposed mask of a masked step in it, and the step's p.
+// post: posterior(x*) needs the factor columns.  Scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N]
+static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post, const double* W, double n_obs, hipStream_t st) {
+    const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M, mx = std::max(m1, m2);
+    VgIter& it = r.it;
+    const bool sc = w.scattered;
+    char oom[256];
+    snprintf(oom, sizeof(oom), "the read-out workspace of the iterative step needs %%.1f GiB at block = %d but only %%.1f GiB of device "
+             "memory are free (a smaller block needs less)", nbc);
+    bool grew = false;
+    const int rc = vg_arena_carve(&w.rmem, &w.rbytes, oom, &grew, [&](VgArena& a) {
+        it.Wt = a.take(sc ? 0 : n1 * n2);
+        it.X = a.take(M * nbc); it.R = a.take(M * nbc); it.Zp = a.take(M * nbc); it.Pd = a.take(M * nbc); it.AP = a.take(M * nbc);
+        it.Tm = a.take(M * nbc); it.Tm2 = a.take(M * nbc); r.T = a.take(M * nbc);
+        it.T1 = a.take(sc ? 0 : n1 * nbc * mx);
+        it.F0 = a.take(sc ? n1 * nbc : n1 * nbc * n2);
+        it.alh = a.take((size_t)nbc); it.beh = a.take((size_t)nbc);
+        it.col = a.take(8 * (size_t)nbc);
+        r.A1 = a.take(post ? m1 * nbc : 0); r.A2 = a.take(post ? m2 * nbc : 0);
+        r.U1 = a.take(post ? m1 * nbc : 0); r.U2 = a.take(post ? m2 * nbc : 0);
+        r.cells = reinterpret_cast<long long*>(a.take((size_t)nbc));
+        it.krs = a.take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
+        it.nact = reinterpret_cast<int*>(a.take(8));
+    });
+    if (rc) return rc;
+    it.nbc = nbc; it.maxit = 1;
+    if (!sc)
+        hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, (long)n1, (long)n2,
+                           it.Wt);
+    r.p = sc ? 1.0 / (double)n1 : n_obs / ((double)n1 * (double)n2);
+    return VGGP_OK;
+}
+
+// Sigma~ X = T for the block in r.T: the step's PCG (vgi_pcg) without the coefficient history and with the two-column field kernel.
+// A function of (the step's operands, r.T) -> r.it.X for either data kind
+static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double tol, int max_iter, int* iters, int* nact, hipStream_t st) {
+    VG_HIP(hipMemcpyAsync(r.it.R, r.T, sizeof(double) * w.M * r.it.nbc, hipMemcpyDeviceToDevice, st));
+    return vgi_pcg(c, w, r.it, r.p, tol, max_iter, /*history=*/false, /*field2=*/true, /*stale_limit=*/0, iters, nact, st);
+}
+// ... and what a read-out entry keeps of it: the number of block solves, the most iterations of one, VGGP_ENOCONV
+static int vgi_solve_block(vggp_ctx* c, VgMasked& w, VgReadout& r, const char* fn, double tol, int max_iter, int* solves, int* max_its,
+                           vggp_info* info, hipStream_t st) {
+    int rc, iters = 0, nact = 0;
+    if ((rc = vgi_readout_solve(c, w, r, tol, max_iter, &iters, &nact, st))) return rc;
+    ++*solves;
+    *max_its = std::max(*max_its, iters);
+    if (info) { info->rounds1 = *max_its; info->sweeps1 = *solves; }
+    if (nact > 0) {
+        vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left, block solve %d)", fn, tol, max_iter, nact, *solves);
+        return VGGP_ENOCONV;
+    }
     return VGGP_OK;
 }
 
@@ -1799,15 +1931,11 @@ static int vgi_readout_solve(vggp_ctx* c, VgMasked& w, VgReadout& r, double p, d
 static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered, const double* W, double n_obs, const int64_t* cells,
                            const double* xs1, const double* xs2, int64_t ncols, double tol, int max_iter, int block, double* mean, double* var,
                            vggp_info* info, void* stream) {
-    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
-    VG_NOT_PAIRED(c, fn);
-    if (scattered) VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: plan the context with VGGP_FLAG_SCATTERED", fn);
-    else VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: the context was planned for scattered points", fn);
-    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
-    const long m1 = c->desc.m1, m2 = c->desc.m2, n1 = c->desc.n1, n2 = c->desc.n2, M = m1 * m2;
+    int rc = vgi_readout_enter(c, fn, scattered, "plan the context with VGGP_FLAG_SCATTERED", "the context was planned for scattered points",
+                               "bad argument", W, n_obs, block);
+    if (rc) return rc;
+    const long m1 = c->desc.m1, m2 = c->desc.m2, M = m1 * m2;
     VG_REQUIRE(ncols >= 0, "%s: bad argument", fn);
-    if (!scattered) VG_REQUIRE(W && std::isfinite(n_obs) && n_obs > 0.0, "%s: bad argument", fn);
-    VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
     if (mode == 0) VG_REQUIRE(xs1 && xs2 && mean && var, "%s: null argument", fn);
     else {
         VG_REQUIRE((ncols == 0 && !var) || (ncols > 0 && var), "%s: var and n_cells must be given together (NULL with 0: mean only)", fn);
@@ -1816,68 +1944,31 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered
             for (int64_t k = 0; k < ncols; ++k)
                 VG_REQUIRE(cells[k] >= 0 && cells[k] < M, "%s: cells[%lld] = %lld is outside [0, M = %ld)", fn, (long long)k, (long long)cells[k], M);
     }
-    auto fits = [&](long b) {
-        return scattered ? (n1 * b < (1L << 31) && M * b < (1L << 31)) : (n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31));
-    };
-    if (block <= 0) { block = 64; while (block > 1 && !fits(block)) block >>= 1; }
-    VG_REQUIRE(fits(block), "%s: problem too large for block = %d", fn, block);
-    if (!c->have_iter || !c->masked) {
-        vg_set_error("%s: no finished %s on this context", fn, scattered ? "vggp_elbo_step_scattered_iter" : "vggp_elbo_step_masked_iter");
-        return VGGP_ESTATE;
-    }
-    if (max_iter <= 0) max_iter = 100;
-    if (!(tol > 0.0)) tol = 1e-10;
-    if (info) { info->jitter1 = info->jitter2 = 0.0; info->sweeps1 = info->sweeps2 = info->rounds1 = info->rounds2 = 0; info->status = 0; info->polished = 0; }
+    if ((rc = vgi_readout_defaults(c, fn, scattered, &block, &tol, &max_iter, info))) return rc;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
     VgDim &d1 = c->d[0], &d2 = c->d[1];
-    int rc;
-    const int e1 = (d1.basis == VGGP_BASIS_VFF || d1.basis == VGGP_BASIS_B1) ? -1 : 1;
-    const int e2 = (d2.basis == VGGP_BASIS_VFF || d2.basis == VGGP_BASIS_B1) ? -1 : 1;
-    if (mode == 1 && mean) {          // the mean of every cell: L0_1 A0 L0_2^T, scaled as vggp_qv_masked scales it
-        if ((rc = gemm1(d1.L0, m1, 1, w.a0, m2, 1, w.MkA1, (int)m2, (int)m1, (int)m2, (int)m1, st))) return rc;
-        if ((rc = gemm1(w.MkA1, m2, 1, d2.L0, 1, m2, mean, (int)m2, (int)m1, (int)m2, (int)m2, st))) return rc;
-        VGM_LAUNCH1D(vgm_scale_rho_kernel, M, st, mean, M, c->theta, e1, e2);
-        VG_HIP(hipGetLastError());
-    }
+    const int e1 = vgi_scale_exp(d1), e2 = vgi_scale_exp(d2);
+    if (mode == 1 && mean && (rc = vgi_qv_mean(c, w, mean, st))) return rc;
     if (ncols == 0) { VG_HIP(hipStreamSynchronize(st)); return VGGP_OK; }
     const int nbc = (int)std::min<int64_t>(block, ncols);
     VgReadout r;
-    if ((rc = vgi_readout_prepare(w, r, nbc, mode == 0))) return rc;
+    if ((rc = vgi_readout_prepare(w, r, nbc, mode == 0, W, n_obs, st))) return rc;
     VgIter& it = r.it;
-    if (!scattered)
-        hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
-    const double p = scattered ? 1.0 / (double)n1 : n_obs / ((double)n1 * (double)n2);
     const long nb = M * nbc;
     int max_its = 0, solves = 0;
     for (int64_t off = 0; off < ncols; off += nbc) {
         const int cn = (int)std::min<int64_t>(nbc, ncols - off);
         if (mode == 0) {
-            VgFactorJob fj[2] = {
-                VgFactorJob{xs1 + off, d1.grid, r.A1, nullptr, nullptr, nullptr, cn, d1.m, d1.kind, d1.basis, 0, 0.0, c->desc.flags},
-                VgFactorJob{xs2 + off, d2.grid, r.A2, nullptr, nullptr, nullptr, cn, d2.m, d2.kind, d2.basis, 1, 0.0, c->desc.flags}};
-            VG_HIP(vg_factor_build_launch(fj, 2, c->theta, st));
-            VgGemmBatch g;
-            vg_gemm_init(&g);
-            vg_gemm_add(&g, d1.Linv0, m1, 1, r.A1, cn, 1, r.U1, cn, (int)m1, cn, (int)m1);
-            vg_gemm_add(&g, d2.Linv0, m2, 1, r.A2, cn, 1, r.U2, cn, (int)m2, cn, (int)m2);
-            VG_HIP(vg_gemm_launch(&g, st));
+            if ((rc = vgi_whitened_columns(c, xs1 + off, xs2 + off, cn, r.A1, r.A2, r.U1, r.U2, st))) return rc;
             VGM_LAUNCH1D(vgi_rank1_kernel, nb, st, r.U1, r.U2, (int)m1, nbc, (int)m2, cn, r.T);
         } else {
             if (cells) VG_HIP(hipMemcpyAsync(r.cells, cells + off, sizeof(long long) * cn, hipMemcpyHostToDevice, st));
             VGM_LAUNCH1D(vgi_rank1_cells_kernel, nb, st, d1.L0, d2.L0, cells ? r.cells : (const long long*)nullptr, (long)off, (int)m1, nbc, (int)m2,
                          cn, r.T);
         }
-        int iters = 0, nact = 0;
-        if ((rc = vgi_readout_solve(c, w, r, p, tol, max_iter, &iters, &nact, st))) return rc;
-        ++solves;
-        max_its = std::max(max_its, iters);
-        if (info) { info->rounds1 = max_its; info->sweeps1 = solves; }
-        if (nact > 0) {
-            vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left, block solve %d)", fn, tol, max_iter, nact, solves);
-            return VGGP_ENOCONV;
-        }
+        if ((rc = vgi_solve_block(c, w, r, fn, tol, max_iter, &solves, &max_its, info, st))) return rc;
         hipLaunchKernelGGL(vgi_readout_reduce_kernel, dim3(cn), dim3(256), 0, st, r.T, it.X, w.a0, (int)m1, nbc, (int)m2, c->theta, mode, e1, e2,
                            mode == 0 ? mean + off : (double*)nullptr, var + off);
     }
@@ -1921,63 +2012,6 @@ __global__ void vgs_scale_mean_kernel(double* x, long n, const double* theta) { 
     if (i < n) x[i] *= theta[2] * theta[3] / theta[4];
 }
 
-struct VgSIter {
-    VgIter it;            // block vectors, PCG state, rotated factors (Rr*, Rv*, RR*, RRV*: [m_d][N]); F0..F2: [nbc][N]; Wt, T1, TW, TWv unused
-    double* krs;          // split scratch of the back kernel
-    double* fpart;        // [1024] partial sums of the field dot products
-};
-
-static int vgs_prepare(VgMasked& w, VgSIter& s, int nbc, int maxit) {
-    const size_t m1 = w.m1, m2 = w.m2, N = w.n1, M = w.M, mx = std::max(m1, m2);
-    VgIter& it = s.it;
-    size_t off = 0;
-    char* base = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-        off = 0;
-        auto take = [&](size_t count) {
-            off = (off + 255) & ~size_t(255);
-            double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-            off += count * sizeof(double);
-            return p;
-        };
-        it.Wt = nullptr; it.T1 = nullptr; it.TW = nullptr; it.TWv = nullptr;
-        it.X = take(M * nbc); it.R = take(M * nbc); it.Zp = take(M * nbc); it.Pd = take(M * nbc); it.AP = take(M * nbc);
-        it.Wz = take(M * nbc); it.Tm = take(M * nbc); it.Tm2 = take(M * nbc);
-        it.F0 = take(N * nbc); it.F1 = take(N * nbc); it.F2 = take(N * nbc);
-        it.alh = take((size_t)maxit * nbc); it.beh = take((size_t)maxit * nbc);
-        it.col = take(8 * (size_t)nbc);
-        it.Rr1 = take(m1 * N); it.Rv1 = take(m1 * N); it.RR1 = take(m1 * N); it.RRV1 = take(m1 * N);
-        it.Rr2 = take(m2 * N); it.Rv2 = take(m2 * N); it.RR2 = take(m2 * N); it.RRV2 = take(m2 * N);
-        it.Ex = take(M);
-        it.dg1 = take(m1); it.dg2 = take(m2); it.Tq = take(mx * mx);
-        it.Qk1 = take(m1 * m1); it.Qk2 = take(m2 * m2);
-        it.ts = take(64 + (size_t)nbc);
-        s.fpart = take(1024);
-        s.krs = take(vg_kr_back_scratch((int)m1, (int)m2, (long)N, nbc));
-        it.nact = reinterpret_cast<int*>(take(8));
-        if (pass == 0) {
-            const size_t need = off + 4096;
-            if (w.ibytes < need || w.ib_nbc != nbc || w.ib_maxit != maxit) w.ib_valid = false;      // (the layout moves: the kept basis is gone)
-            w.ib_nbc = nbc; w.ib_maxit = maxit;
-            if (w.ibytes < need) {
-                if (w.imem) { VG_HIP(hipFree(w.imem)); w.imem = nullptr; w.ibytes = 0; }
-                size_t free_b = 0, total_b = 0;
-                if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-                    vg_set_error("the workspace of the iterative scattered step needs %.1f GiB (m1 = %d, m2 = %d, N = %ld, %d columns) but only "
-                                 "%.1f GiB of device memory are free", (double)need / 1073741824.0, w.m1, w.m2, (long)N, nbc,
-                                 (double)free_b / 1073741824.0);
-                    return VGGP_ENOMEM;
-                }
-                VG_HIP(hipMalloc(&w.imem, need));
-                w.ibytes = need;
-            }
-            base = reinterpret_cast<char*>(w.imem);
-        }
-    }
-    it.nbc = nbc; it.maxit = maxit;
-    return VGGP_OK;
-}
-
 // entry checks shared by the step and its read-outs
 static int vgs_check(vggp_ctx* c, const char* fn) {
     if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
@@ -2010,9 +2044,8 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     }
     if ((rc = vgm_prepare(c, /*iter=*/true))) return rc;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
-    VgSIter s;
-    if ((rc = vgs_prepare(w, s, nbc, max_iter))) return rc;
-    VgIter& it = s.it;
+    VgIter it;
+    if ((rc = vgi_prepare(w, it, nbc, max_iter))) return rc;
     if ((rc = vg_partials_enqueue(c, nullptr, nullptr, st))) return rc;          // factors at the points: B|V, Mk (unit outputscale)
     VgDim &d1 = c->d[0], &d2 = c->d[1];
     const double *B1 = d1.BV, *V1 = d1.BV + m1 * N, *B2 = d2.BV, *V2 = d2.BV + m2 * N;
@@ -2031,85 +2064,11 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     if ((rc = gemm_longk(B1, N, 1, B1, 1, N, d1.GH, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
     if ((rc = gemm_longk(B2, N, 1, B2, 1, N, d2.GH, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
     bool reused = false;
-    {   // eigenbasis of the preconditioner: the kept-basis rules of the masked iterative step (see there)
-        static const bool always = getenv("VGGP_ITER_COLD_BASIS") != nullptr;
-        const double* G[2] = {d1.GH, d2.GH};
-        const bool reuse = !always && w.ib_valid && w.ib_age < 64 && w.ib_last_its <= w.ib_ref_its + 4 && d1.kind != VGGP_KIND_RBF &&
-                           d2.kind != VGGP_KIND_RBF;
-        reused = reuse;
-        if (reuse) {
-            double* Qk[2] = {it.Qk1, it.Qk2};
-            for (int k = 0; k < 2; ++k) {
-                VgDim& d = c->d[k];
-                VG_HIP(hipMemcpyAsync(d.Qt, Qk[k], sizeof(double) * d.m * d.m, hipMemcpyDeviceToDevice, st));
-                if ((rc = gemm1(d.Qt, d.m, 1, G[k], d.m, 1, it.Tq, d.m, d.m, d.m, d.m, st))) return rc;
-                VGM_LAUNCH1D(vgi_rowdot_kernel, d.m, st, it.Tq, d.Qt, d.m, d.lam0);
-            }
-            ++w.ib_age;
-            w.ib_fresh = false;
-        } else {
-            VgEigJob ej[2];
-            for (int k = 0; k < 2; ++k) {
-                VgDim& d = c->d[k];
-                ej[k] = VgEigJob{G[k], d.lam0, d.Qt, nullptr, d.gwork, d.rotlog, d.roundlog, d.counters, d.m, d.max_rounds,
-                                 (long)vg_eigh_log_bytes(d.m), 0};
-                ej[k].perm = d.perm;
-                ej[k].err = d.status + 1;
-            }
-            VG_HIP(vg_eigh_launch(ej, 2, st));
-            VG_HIP(hipMemcpyAsync(it.Qk1, d1.Qt, sizeof(double) * m1 * m1, hipMemcpyDeviceToDevice, st));
-            VG_HIP(hipMemcpyAsync(it.Qk2, d2.Qt, sizeof(double) * m2 * m2, hipMemcpyDeviceToDevice, st));
-            w.ib_valid = false;
-            w.ib_fresh = true;
-        }
-    }
+    if ((rc = vgi_basis(c, w, it, d1.GH, d2.GH, &reused, st))) return rc;
     const double p = 1.0 / (double)N;
-    const long nb = M * nbc, nf = N * nbc;
-    auto field = [&](const double* L, const double* V, const double* R, double* F) -> int {
-        VG_HIP(vg_kr_field_launch(L, R, V, (int)m1, (int)m2, N, nbc, F, st));
-        return VGGP_OK;
-    };
-    VGM_LAUNCH1D(vgi_probe_kernel, nb, st, it.X, (int)m1, nbc, (int)m2, 0x5647475000000001ULL);
-    if ((rc = vgi_rot(c, w, it, it.X, it.R, 1, 1, p, st))) return rc;
-    if ((rc = vgi_rot(c, w, it, it.X, it.Wz, 2, 1, p, st))) return rc;
-    VGM_LAUNCH1D(vgi_col_kernel, M, st, it.R, C0, (int)m1, nbc, (int)m2, 0, 0);
-    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
-    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col, it.col + 3 * nbc);
-    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
-    int iters = 0, nact = nbc;
-    for (int k = 0; k < max_iter && nact > 0; ++k) {
-        // AP = Pd + rho sum_k b1_k (b1_k^T Pd b2_k) b2_k^T
-        if ((rc = field(B1, it.Pd, B2, it.F0))) return rc;
-        VG_HIP(vg_kr_back_launch(B1, B2, it.F0, (int)m1, (int)m2, N, nbc, it.AP, s.krs, st));
-        VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                           (int)m2, it.col + nbc, (double*)nullptr);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, k, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 1);
-        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, (int)m1, nbc, (int)m2, it.col + 5 * nbc,
-                           it.col + 3 * nbc);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, k, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, (int)m1, nbc, (int)m2, 2);
-        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipStreamSynchronize(st));
-        nact = c->h_out->counters[0][0];
-        iters = k + 1;
-        if (reused && nact > 0 && iters > w.ib_ref_its + 12) {      // the kept basis has drifted too far: not worth iterating on
-            w.ib_valid = false;
-            return VGI_ESTALE;
-        }
-    }
-    if (nact > 0) { vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left)", fn, tol, max_iter, nact); return VGGP_ENOCONV; }
-    // log det: log|P| + the quadratures
-    VG_HIP(hipMemsetAsync(it.ts, 0, 64 * sizeof(double), st));
-    VG_HIP(hipMemsetAsync(w.cholstatus, 0, sizeof(int), st));
-    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr,
-                       (const double*)nullptr, (const double*)nullptr, 1, it.ts + 0);
-    hipLaunchKernelGGL(vgi_slq_kernel, dim3(1), dim3(64), 0, st, it.alh, it.beh, it.col, nbc, (double)M, it.ts + 32, w.cholstatus);
-    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.ts + 32, n_probes, it.ts + 1, 0);
+    int iters = 0;
+    if ((rc = vgi_step_solve(c, w, it, fn, C0, p, tol, max_iter, reused, &iters, st))) return rc;
+    if ((rc = vgi_logdet(c, w, it, p, st))) return rc;
     // a0 and the a0 terms of the gradient (the dense scattered step's)
     VGM_LAUNCH1D(vgi_col_kernel, M, st, it.X, w.a0, (int)m1, nbc, (int)m2, 0, 1);
     if ((rc = gemm1(d1.Mk, m1, 1, w.a0, m2, 1, w.MkA1, (int)m2, (int)m1, (int)m2, (int)m1, st))) return rc;
@@ -2123,124 +2082,46 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     VGM_LAUNCH1D(vgm_scalecols_kernel, m2 * N, st, B2, w.nb1, (int)m2, N, w.B2s);
     if ((rc = gemm_longk(w.B1s, N, 1, B1, 1, N, w.PT1, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
     if ((rc = gemm_longk(w.B2s, N, 1, B2, 1, N, w.PT2, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
-    // dU = Sigma~^-1 z - P^-1 z (probe columns); stochastic parts of the traces: per-point fields of dU and of Wz
-    VGM_LAUNCH1D(vgi_sub_kernel, nb, st, it.X, it.Wz, nb, it.Zp);
-    double* dU = it.Zp;
-    auto fsum = [&](const double* Fa, const double* Fb, double* out) {          // sum over the probe columns c >= 1 and the points
-        hipLaunchKernelGGL(vgs_dot_part_kernel, dim3(1024), dim3(256), 0, st, Fa + N, Fb + N, nf - N, s.fpart);
-        hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, s.fpart, 1024, out, 0);
+    // dU = Sigma~^-1 z - P^-1 z (probe columns); the control variates' fields are per-point vectors [nbc][N]
+    VGM_LAUNCH1D(vgi_sub_kernel, M * nbc, st, it.X, it.Wz, M * nbc, it.Zp);
+    const double* dU = it.Zp;
+    auto field = [&](const double* L, const double* V, const double* R, double* F) -> int {
+        VG_HIP(vg_kr_field_launch(L, R, V, (int)m1, (int)m2, N, nbc, F, st));
+        return VGGP_OK;
     };
-    if ((rc = field(B1, it.Wz, B2, it.F0))) return rc;              // F0 = Fw^BB
-    if ((rc = field(B1, dU, B2, it.F1))) return rc;                 // F1 = Fu^BB
-    fsum(it.F1, it.F0, it.ts + 3);
-    if ((rc = field(V1, dU, B2, it.F2))) return rc;                 // Fu^VB
-    fsum(it.F2, it.F0, it.ts + 6);
-    if ((rc = field(B1, dU, V2, it.F2))) return rc;                 // Fu^BV
-    fsum(it.F2, it.F0, it.ts + 9);
-    if ((rc = field(V1, it.Wz, B2, it.F0))) return rc;              // Fw^VB
-    fsum(it.F1, it.F0, it.ts + 5);
-    if ((rc = field(B1, it.Wz, V2, it.F0))) return rc;              // Fw^BV
-    fsum(it.F1, it.F0, it.ts + 8);
-    // Mk terms: <dU, Mk1 Wz>, <dU, Wz Mk2^T>
-    double* cs = it.ts + 64;                                        // [nbc] per-column sums
-    if ((rc = gemm1(d1.Mk, m1, 1, it.Wz, (long)nbc * m2, 1, it.Tm, nbc * (int)m2, (int)m1, nbc * (int)m2, (int)m1, st))) return rc;
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                       (int)m2, cs, (double*)nullptr);
-    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, cs, nbc, it.ts + 11, 1);
-    if ((rc = gemm1(it.Wz, m2, 1, d2.Mk, 1, m2, it.Tm, (int)m2, (int)(m1 * nbc), (int)m2, (int)m2, st))) return rc;
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, dU, it.Tm, (const double*)nullptr, (const double*)nullptr, (int)m1, nbc,
-                       (int)m2, cs, (double*)nullptr);
-    hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, cs, nbc, it.ts + 13, 1);
-    // exact parts tr(P^-1 Phi(.)) = sum (1/dP) o ((Ra o Rb)(Sa o Sb)^T): factors rotated into the eigenbasis of P, one m1 x m2 GEMM
-    // over the points each
-    if ((rc = gemm1(d1.Qt, m1, 1, B1, N, 1, it.Rr1, (int)N, (int)m1, (int)N, (int)m1, st))) return rc;
-    if ((rc = gemm1(d1.Qt, m1, 1, V1, N, 1, it.Rv1, (int)N, (int)m1, (int)N, (int)m1, st))) return rc;
-    if ((rc = gemm1(d2.Qt, m2, 1, B2, N, 1, it.Rr2, (int)N, (int)m2, (int)N, (int)m2, st))) return rc;
-    if ((rc = gemm1(d2.Qt, m2, 1, V2, N, 1, it.Rv2, (int)N, (int)m2, (int)N, (int)m2, st))) return rc;
-    VGM_LAUNCH1D(vgi_mul_kernel, m1 * N, st, it.Rr1, it.Rr1, m1 * N, it.RR1);
-    VGM_LAUNCH1D(vgi_mul_kernel, m1 * N, st, it.Rr1, it.Rv1, m1 * N, it.RRV1);
-    VGM_LAUNCH1D(vgi_mul_kernel, m2 * N, st, it.Rr2, it.Rr2, m2 * N, it.RR2);
-    VGM_LAUNCH1D(vgi_mul_kernel, m2 * N, st, it.Rr2, it.Rv2, m2 * N, it.RRV2);
+    auto fsum = [&](const double* Fa, const double* Fb, double* out) {          // sum over the probe columns c >= 1 and the points
+        hipLaunchKernelGGL(vgs_dot_part_kernel, dim3(1024), dim3(256), 0, st, Fa + N, Fb + N, N * nbc - N, it.fpart);
+        hipLaunchKernelGGL(vgi_sum_kernel, dim3(1), dim3(64), 0, st, it.fpart, 1024, out, 0);
+    };
+    if ((rc = vgi_field_terms(c, w, it, dU, field, fsum))) return rc;
+    if ((rc = vgi_mk_terms(c, w, it, dU, st))) return rc;
+    // exact parts tr(P^-1 Phi(.)) = sum (1/dP) o ((Ra o Rb)(Sa o Sb)^T): one m1 x m2 GEMM over the points each
+    if ((rc = vgi_rotate_factors(c, w, it, st))) return rc;
     auto exact = [&](const double* RRa, const double* RRb, double* out) -> int {
         int r2 = gemm_longk(RRa, N, 1, RRb, 1, N, it.Ex, (int)m1, (int)m2, (int)N, w.T, st);
         if (r2) return r2;
-        hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, it.Ex,
-                           (const double*)nullptr, (const double*)nullptr, 0, out);
+        vgi_exact_sum(c, w, it, p, out, st);
         return VGGP_OK;
     };
     if ((rc = exact(it.RR1, it.RR2, it.ts + 2))) return rc;
     if ((rc = exact(it.RRV1, it.RR2, it.ts + 4))) return rc;
     if ((rc = exact(it.RR1, it.RRV2, it.ts + 7))) return rc;
-    if ((rc = gemm1(d1.Qt, m1, 1, d1.Mk, m1, 1, it.Tq, (int)m1, (int)m1, (int)m1, (int)m1, st))) return rc;
-    VGM_LAUNCH1D(vgi_rowdot_kernel, m1, st, it.Tq, d1.Qt, (int)m1, it.dg1);
-    if ((rc = gemm1(d2.Qt, m2, 1, d2.Mk, m2, 1, it.Tq, (int)m2, (int)m2, (int)m2, (int)m2, st))) return rc;
-    VGM_LAUNCH1D(vgi_rowdot_kernel, m2, st, it.Tq, d2.Qt, (int)m2, it.dg2);
-    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr, it.dg1,
-                       (const double*)nullptr, 0, it.ts + 10);
-    hipLaunchKernelGGL(vgi_dpsum_kernel, dim3(1), dim3(256), 0, st, d1.lam0, d2.lam0, c->theta, p, (int)m1, (int)m2, (const double*)nullptr,
-                       (const double*)nullptr, it.dg2, 0, it.ts + 12);
-    // the dense scattered step's reductions that do not involve Sigma~^-1 as a matrix; the six that do come from the combine kernel
+    if ((rc = vgi_mk_traces(c, w, it, p, st))) return rc;
     VgmRedArgs ra;
-    ra.njobs = RJ_COUNT;
-    ra.partial = w.partial;
-    auto job = [&](int k, const double* a, const double* b, long n, long sa, long sb, int op) {
-        ra.job[k] = VgmRedJob{a, b, nullptr, n, sa, sb, op};
-    };
-    for (int k = 0; k < RJ_COUNT; ++k) job(k, w.a0, w.a0, 0, 1, 1, 0);
-    job(RJ_Q, C0, w.a0, M, 1, 1, 0);
-    job(RJ_AA, w.a0, w.a0, M, 1, 1, 0);
-    job(RJ_TRPHI, w.nb1, w.nb2, N, 1, 1, 0);
-    job(RJ_TRMK1, d1.Mk, nullptr, m1, m1 + 1, 0, 2);
-    job(RJ_AC1, w.a0, C1, M, 1, 1, 0);
-    job(RJ_MKA1, w.MkA1, w.a0, M, 1, 1, 0);
-    job(RJ_Z1, w.Zb, w.Zv1, N, 1, 1, 0);
-    job(RJ_HV1, w.hv1, w.nb2, N, 1, 1, 0);
-    job(RJ_MK1PT, d1.Mk, w.PT1, m1 * m1, 1, 1, 0);
-    job(RJ_TRMK2, d2.Mk, nullptr, m2, m2 + 1, 0, 2);
-    job(RJ_AC2, w.a0, C2, M, 1, 1, 0);
-    job(RJ_MKA2, w.MkA2, w.a0, M, 1, 1, 0);
-    job(RJ_Z2, w.Zb, w.Zv2, N, 1, 1, 0);
-    job(RJ_HV2, w.hv2, w.nb1, N, 1, 1, 0);
-    job(RJ_MK2PT, d2.Mk, w.PT2, m2 * m2, 1, 1, 0);
-    hipLaunchKernelGGL(vgm_red_kernel, dim3(VG_MD_NPART, RJ_COUNT), dim3(256), 0, st, ra);
-    hipLaunchKernelGGL(vgm_sum_kernel, dim3(1), dim3(64), 0, st, w.partial, w.scal, 0u, 1);
-    hipLaunchKernelGGL(vgi_combine_kernel, dim3(1), dim3(64), 0, st, it.ts, c->theta, (double)M, n_probes, w.scal);
-    VgmFinalArgs fa{c->theta, w.scal, w.out, (double)N, yy, (int)m1, (int)m2};
-    hipLaunchKernelGGL(vgm_final_kernel, dim3(1), dim3(64), 0, st, fa);
-    VG_HIP(hipGetLastError());
-    VG_HIP(hipMemcpyAsync(c->h_out->out, w.out, 8 * sizeof(double), hipMemcpyDeviceToHost, st));
-    for (int k = 0; k < 2; ++k) {
-        VG_HIP(hipMemcpyAsync(&c->h_out->jitter[k], c->d[k].jitter, sizeof(double), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipMemcpyAsync(&c->h_out->status[k], c->d[k].status, sizeof(int), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipMemcpyAsync(&c->h_out->counters[k][2], c->d[k].counters + 2, sizeof(int), hipMemcpyDeviceToHost, st));
-    }
-    VG_HIP(hipMemcpyAsync(&c->h_out->counters[1][3], w.cholstatus, sizeof(int), hipMemcpyDeviceToHost, st));
-    VG_HIP(hipStreamSynchronize(st));
-    *elbo_out = c->h_out->out[0];
-    for (int i = 0; i < 5; ++i) grad_out[i] = c->h_out->out[1 + i];
-    int status = c->h_out->status[0] ? c->h_out->status[0] : (c->h_out->status[1] ? c->h_out->status[1] : 0);
-    if (!status) status = c->h_out->counters[0][2] ? c->h_out->counters[0][2] : c->h_out->counters[1][2];
-    if (info) {
-        info->jitter1 = c->h_out->jitter[0]; info->jitter2 = c->h_out->jitter[1];
-        info->sweeps1 = n_probes; info->sweeps2 = 0; info->rounds1 = iters; info->rounds2 = 0;
-        info->status = status; info->polished = 0;
-    }
-    if (status == VGGP_ENOTPD) { vg_set_error("iterative scattered step: a factor is not positive definite"); return VGGP_ENOTPD; }
-    if (status) { vg_set_error("iterative scattered step: the preconditioner's eigensolver failed (status %d)", status); return VGGP_ENOCONV; }
-    if (c->h_out->counters[1][3]) { vg_set_error("iterative scattered step: the Lanczos quadrature failed (code %d)", c->h_out->counters[1][3]); return VGGP_ENOCONV; }
-    if (w.ib_fresh) { w.ib_valid = true; w.ib_age = 0; w.ib_ref_its = iters; }
-    w.ib_last_its = iters;
-    c->have_step = false; c->have_partials = false;
-    c->have_iter = true;             // a0 and the factors are there for vggp_qv_scattered_iter / vggp_posterior_scattered_iter
-    return VGGP_OK;
+    vgi_red_jobs(c, w, C0, ra);
+    vgi_red_job(ra, RJ_TRPHI, w.nb1, w.nb2, N, 1, 1, 0);
+    vgi_red_job(ra, RJ_Z1, w.Zb, w.Zv1, N, 1, 1, 0);
+    vgi_red_job(ra, RJ_HV1, w.hv1, w.nb2, N, 1, 1, 0);
+    vgi_red_job(ra, RJ_Z2, w.Zb, w.Zv2, N, 1, 1, 0);
+    vgi_red_job(ra, RJ_HV2, w.hv2, w.nb1, N, 1, 1, 0);
+    return vgi_finish(c, w, it, "scattered", ra, (double)N, yy, iters, elbo_out, grad_out, info, st);
 }
 
 extern "C" int vggp_elbo_step_scattered_iter(vggp_ctx* c, const double* y, double yy, const double theta[5], int n_probes, double tol,
                                              int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream) {
-    int rc = scattered_iter_once(c, y, yy, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
-    if (rc == VGI_ESTALE) rc = scattered_iter_once(c, y, yy, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
-    if (rc == VGI_ESTALE) { vg_set_error("vggp_elbo_step_scattered_iter: internal (stale basis after a cold solve)"); rc = VGGP_ESTATE; }
-    return rc;
+    return vgi_retry_stale("vggp_elbo_step_scattered_iter", [&] {
+        return scattered_iter_once(c, y, yy, theta, n_probes, tol, max_iter, elbo_out, grad_out, info, stream);
+    });
 }
 
 // q(v) mean of the last iterative scattered step: (s1 s2 / v) L1 A0 L2^T, scaled as vggp_qv_masked_iter scales it (no solve)
@@ -2253,14 +2134,7 @@ extern "C" int vggp_qv_scattered_iter(vggp_ctx* c, double* mean, void* stream) {
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
-    VgDim &d1 = c->d[0], &d2 = c->d[1];
-    const long m1 = w.m1, m2 = w.m2, M = w.M;
-    const int e1 = (d1.basis == VGGP_BASIS_VFF || d1.basis == VGGP_BASIS_B1) ? -1 : 1;
-    const int e2 = (d2.basis == VGGP_BASIS_VFF || d2.basis == VGGP_BASIS_B1) ? -1 : 1;
-    if ((rc = gemm1(d1.L0, m1, 1, w.a0, m2, 1, w.MkA1, (int)m2, (int)m1, (int)m2, (int)m1, st))) return rc;
-    if ((rc = gemm1(w.MkA1, m2, 1, d2.L0, 1, m2, mean, (int)m2, (int)m1, (int)m2, (int)m2, st))) return rc;
-    VGM_LAUNCH1D(vgm_scale_rho_kernel, M, st, mean, M, c->theta, e1, e2);
-    VG_HIP(hipGetLastError());
+    if ((rc = vgi_qv_mean(c, w, mean, st))) return rc;
     VG_HIP(hipStreamSynchronize(st));
     return VGGP_OK;
 }
@@ -2276,7 +2150,6 @@ extern "C" int vggp_posterior_scattered_iter(vggp_ctx* c, const double* xs1, con
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
-    VgDim &d1 = c->d[0], &d2 = c->d[1];
     const long m1 = w.m1, m2 = w.m2;
     const long chunk = std::min<long>(ns, 1L << 16);
     if ((rc = vg_ensure_misc(c, (size_t)chunk * (3 * m1 + 2 * m2) * sizeof(double)))) return rc;
@@ -2288,15 +2161,7 @@ extern "C" int vggp_posterior_scattered_iter(vggp_ctx* c, const double* xs1, con
     double* U2 = p;
     for (long off = 0; off < ns; off += chunk) {
         const int cn = (int)std::min<long>(chunk, ns - off);
-        VgFactorJob fj[2] = {
-            VgFactorJob{xs1 + off, d1.grid, A1, nullptr, nullptr, nullptr, cn, d1.m, d1.kind, d1.basis, 0, 0.0, c->desc.flags},
-            VgFactorJob{xs2 + off, d2.grid, A2, nullptr, nullptr, nullptr, cn, d2.m, d2.kind, d2.basis, 1, 0.0, c->desc.flags}};
-        VG_HIP(vg_factor_build_launch(fj, 2, c->theta, st));
-        VgGemmBatch g;
-        vg_gemm_init(&g);
-        vg_gemm_add(&g, d1.Linv0, m1, 1, A1, cn, 1, U1, cn, (int)m1, cn, (int)m1);
-        vg_gemm_add(&g, d2.Linv0, m2, 1, A2, cn, 1, U2, cn, (int)m2, cn, (int)m2);
-        VG_HIP(vg_gemm_launch(&g, st));
+        if ((rc = vgi_whitened_columns(c, xs1 + off, xs2 + off, cn, A1, A2, U1, U2, st))) return rc;
         if ((rc = gemm1(w.a0, m2, 1, U2, cn, 1, T, cn, (int)m1, cn, (int)m2, st))) return rc;                   // A0 U2
         VGM_LAUNCH1D(vgm_coldot_kernel, cn, st, U1, T, (int)m1, (long)cn, mean + off);
         VGM_LAUNCH1D(vgs_scale_mean_kernel, cn, st, mean + off, (long)cn, c->theta);
@@ -2438,17 +2303,14 @@ __global__ void vgi_readout_literal_kernel(const double* S, const double* kd1, c
 static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, const double* C1, int64_t mv1,
                            const double* C2, int64_t mv2, const double* kd1, const double* kd2, const int64_t* cells, int64_t n_cells,
                            double tol, int max_iter, int block, double* mean, double* var, int flags, vggp_info* info, void* stream) {
-    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
-    VG_NOT_PAIRED(c, fn);
-    if (scattered) VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: the context was planned for a grid (vggp_readout_masked_iter reads those)", fn);
-    else VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: the context was planned for scattered points (vggp_readout_scattered_iter reads those)", fn);
-    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
+    int rc = vgi_readout_enter(c, fn, scattered, "the context was planned for a grid (vggp_readout_masked_iter reads those)",
+                               "the context was planned for scattered points (vggp_readout_scattered_iter reads those)", "bad argument (W, n_obs)",
+                               W, n_obs, block);
+    if (rc) return rc;
     const long m1 = c->desc.m1, m2 = c->desc.m2, n1 = c->desc.n1, n2 = c->desc.n2, M = m1 * m2;
     VG_REQUIRE(C1 && C2 && kd1 && kd2 && mv1 > 0 && mv2 > 0 && mv1 < (1L << 20) && mv2 < (1L << 20) && mv1 * mv2 < (1L << 28) && n_cells >= 0,
                "%s: bad argument (C_d, kd_d non-null, mv_d >= 1, mv1 mv2 < 2^28)", fn);
     const long ncell_all = mv1 * mv2;
-    if (!scattered) VG_REQUIRE(W && std::isfinite(n_obs) && n_obs > 0.0, "%s: bad argument (W, n_obs)", fn);
-    VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
     VG_REQUIRE((n_cells == 0 && !var) || (n_cells > 0 && var), "%s: var and n_cells must be given together (NULL with 0: mean only)", fn);
     VG_REQUIRE(mean || var, "%s: nothing to compute (mean and var are NULL)", fn);
     VG_REQUIRE(cells || n_cells == 0 || n_cells == ncell_all, "%s: cells = NULL means every cell: n_cells must be mv1 mv2 = %ld", fn, ncell_all);
@@ -2456,18 +2318,7 @@ static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const do
         for (int64_t k = 0; k < n_cells; ++k)
             VG_REQUIRE(cells[k] >= 0 && cells[k] < ncell_all, "%s: cells[%lld] = %lld is outside [0, mv1 mv2 = %ld)", fn, (long long)k,
                        (long long)cells[k], ncell_all);
-    auto fits = [&](long b) {
-        return scattered ? (n1 * b < (1L << 31) && M * b < (1L << 31)) : (n1 * b * n2 < (1L << 31) * 4 && n1 * b < (1L << 31) && M * b < (1L << 31));
-    };
-    if (block <= 0) { block = 64; while (block > 1 && !fits(block)) block >>= 1; }
-    VG_REQUIRE(fits(block), "%s: problem too large for block = %d", fn, block);
-    if (!c->have_iter || !c->masked) {
-        vg_set_error("%s: no finished %s on this context", fn, scattered ? "vggp_elbo_step_scattered_iter" : "vggp_elbo_step_masked_iter");
-        return VGGP_ESTATE;
-    }
-    if (max_iter <= 0) max_iter = 100;
-    if (!(tol > 0.0)) tol = 1e-10;
-    if (info) { info->jitter1 = info->jitter2 = 0.0; info->sweeps1 = info->sweeps2 = info->rounds1 = info->rounds2 = 0; info->status = 0; info->polished = 0; }
+    if ((rc = vgi_readout_defaults(c, fn, scattered, &block, &tol, &max_iter, info))) return rc;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
@@ -2488,7 +2339,7 @@ static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const do
     const size_t oU1 = room(m1 * mv1), oU2 = room(m2 * mv2), oTm = room(mv1 * std::max(m2, lit && !scattered ? n2 : 0L));
     const size_t oCells = room(cells ? (size_t)n_cells : 0);
     const size_t oP1 = room(mv1 * np1), oP2 = room(mv2 * np2), oS = room(lit ? ncell_all : 0), oSq = room(sq);
-    int rc = vg_ensure_misc(c, need * sizeof(double));
+    rc = vg_ensure_misc(c, need * sizeof(double));
     if (rc) return rc;
     double* base = (double*)c->misc;
     double *U1 = base + oU1, *U2 = base + oU2, *Tm = base + oTm, *P1 = base + oP1, *P2 = base + oP2, *S = base + oS, *Sq = base + oSq;
@@ -2538,27 +2389,15 @@ static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const do
     }
     const int nbc = (int)std::min<int64_t>(block, n_cells);
     VgReadout r;
-    if ((rc = vgi_readout_prepare(w, r, nbc, false))) return rc;
-    VgIter& it = r.it;
-    if (!scattered)
-        hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
-    const double p = scattered ? 1.0 / (double)n1 : n_obs / ((double)n1 * (double)n2);
+    if ((rc = vgi_readout_prepare(w, r, nbc, false, W, n_obs, st))) return rc;
     const long nb = M * nbc;
     int max_its = 0, solves = 0;
     for (int64_t off = 0; off < n_cells; off += nbc) {
         const int cn = (int)std::min<int64_t>(nbc, n_cells - off);
         const long long* cl = dcells ? dcells + off : nullptr;
         VGM_LAUNCH1D(vgi_rank1_grid_kernel, nb, st, U1, U2, cl, (long)off, (int)m1, nbc, (int)m2, (long)mv1, (long)mv2, cn, r.T);
-        int iters = 0, nact = 0;
-        if ((rc = vgi_readout_solve(c, w, r, p, tol, max_iter, &iters, &nact, st))) return rc;
-        ++solves;
-        max_its = std::max(max_its, iters);
-        if (info) { info->rounds1 = max_its; info->sweeps1 = solves; }
-        if (nact > 0) {
-            vg_set_error("%s: PCG did not reach %.1e in %d iterations (%d columns left, block solve %d)", fn, tol, max_iter, nact, solves);
-            return VGGP_ENOCONV;
-        }
-        hipLaunchKernelGGL(vgi_readout_reduce_grid_kernel, dim3(cn), dim3(256), 0, st, r.T, it.X, (int)m1, nbc, (int)m2, c->theta, kd1, kd2, cl,
+        if ((rc = vgi_solve_block(c, w, r, fn, tol, max_iter, &solves, &max_its, info, st))) return rc;
+        hipLaunchKernelGGL(vgi_readout_reduce_grid_kernel, dim3(cn), dim3(256), 0, st, r.T, r.it.X, (int)m1, nbc, (int)m2, c->theta, kd1, kd2, cl,
                            (long)off, (long)mv2, var + off);
     }
     VG_HIP(hipGetLastError());
