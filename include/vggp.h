@@ -196,7 +196,18 @@ int vggp_elbo_step_masked(vggp_ctx* ctx, const double* Ym, const double* W, doub
  * quadrature of the PCG coefficients of n_probes FIXED Rademacher probes, and derivative traces as closed form + control-variate
  * probe estimator.  Bitwise reproducible.  Stated tolerance against vggp_elbo_step_masked: ELBO 1e-5 relative, gradient 1e-4 of
  * its largest component (n_probes = 16).  n_probes <= 0: 16; tol <= 0: 1e-10 (PCG residual, relative); max_iter <= 0: 100.
- * Arguments otherwise as vggp_elbo_step_masked; single-rank contexts; info->rounds1 = PCG iterations, info->sweeps1 = probes.
+ * Arguments otherwise as vggp_elbo_step_masked; info->rounds1 = PCG iterations, info->sweeps1 = probes.
+ * Multi-rank context (the split of vggp_elbo_step_masked): LOCAL are the row slab Ym[rows], W[rows] and the plan's x2[rows];
+ * GLOBAL are n_obs, yy_obs and desc.n_total = n1 n2 over all ranks (the preconditioner's observed fraction is n_obs / n_total);
+ * REPLICATED are the block vectors, probes, preconditioner, its kept basis and every PCG scalar.  Collectives, on the step's
+ * stream and in the same order on every rank: one packed all-reduce before the solve (G2, H2 | C, C1, C2 | a column statistic:
+ * 2 m2^2 + 3 M + n1 doubles), one all-reduce of the partial operator product per PCG iteration (M (n_probes + 1) doubles), one
+ * packed all-reduce of 32 scalars after the solve (the sums over grid rows: reduction jobs, control-variate field sums, exact-trace
+ * products).  Every host decision (iteration count, kept or cold basis, VGGP_ENOCONV, status) is taken from replicated data, so
+ * all ranks return the same code from the same call with bitwise equal results; host waits poll the communicator.
+ * That holds only over a transport that really sums over the n_ranks ranks of vggp_create: the first iterative entry (step or
+ * read-out) called on a multi-rank context all-reduces the single value 1.0, once per context and transport, and every iterative
+ * entry returns VGGP_EINVAL when it does not come back as n_ranks (a callback that sums nothing, a communicator of another size).
  * Its read-outs are vggp_qv_masked_iter and vggp_posterior_masked_iter below (the dense ones, vggp_qv_masked, ..., return
  * VGGP_ESTATE after this step: there is no Sigma~^-1 to read). */
 int vggp_elbo_step_masked_iter(vggp_ctx* ctx, const double* Ym, const double* W, double n_obs, double yy_obs,
@@ -212,7 +223,9 @@ int vggp_elbo_step_masked_iter(vggp_ctx* ctx, const double* Ym, const double* W,
  *   info       (may be NULL) rounds1 = largest PCG iteration count over the block solves, sweeps1 = number of block solves
  * Both return VGGP_ESTATE unless the LAST finished step on the context was a successful vggp_elbo_step_masked_iter (vggp_plan,
  * vggp_set_inducing, any other step and a failed iterative step end that state); VGGP_ENOCONV when a column does not converge;
- * VGGP_EINVAL on paired, scattered or multi-rank contexts, a cell index outside [0, M), block > 64.  The workspace (block
+ * VGGP_EINVAL on paired or scattered contexts, a cell index outside [0, M), block > 64.  Multi-rank context: W is the rank's
+ * row slab, n_obs global; right-hand sides and results are replicated, and the only collective is the operator's all-reduce of each
+ * PCG iteration (every rank must make the same call).  The workspace (block
  * vectors and one n1 x block x n2 field) is allocated on first use and apart from the step's: a read-out leaves the step's kept
  * preconditioner basis valid and the next step's results unchanged.
  *
@@ -242,14 +255,18 @@ int vggp_posterior_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, con
  * The stochastic ELBO and gradient match the iterative masked step's quality (ELBO 1e-5 relative, gradient 1e-4 of its largest
  * component against vggp_elbo_step_scattered, 16 probes) when the points outnumber the inducing features by about 60 or more;
  * they degrade to 1e-3 .. 1e-2 when N is about M, where few tracks also cost PCG iterations.  No tolerance is stated there.
- * Needs a context planned with VGGP_FLAG_SCATTERED (VGGP_EINVAL otherwise, and on paired or multi-rank contexts); VGGP_ENOCONV when
- * the PCG does not converge.  The kept-basis rules are the masked iterative step's (VGGP_ITER_COLD_BASIS honoured).  The dense
+ * Needs a context planned with VGGP_FLAG_SCATTERED (VGGP_EINVAL otherwise, and on paired contexts); VGGP_ENOCONV when
+ * the PCG does not converge.  Multi-rank context (the split of vggp_elbo_step_scattered): LOCAL are the rank's own points x, y (any
+ * share); GLOBAL are yy and desc.n_total = N over all ranks (p = 1 / n_total); REPLICATED is everything in M-space.  Collectives as
+ * vggp_elbo_step_masked_iter: before the solve G2 | C, C1, C2 | G1 in one call, per PCG iteration the partial operator product,
+ * after the solve 32 scalars (the sums over points, PT1 and PT2 through their scalars <Mk_d, PT_d>); the same host decisions on
+ * every rank.  The kept-basis rules are the masked iterative step's (VGGP_ITER_COLD_BASIS honoured).  The dense
  * read-outs (vggp_qv_masked, ...) and vggp_zgrad_scattered return VGGP_ESTATE after this step. */
 int vggp_elbo_step_scattered_iter(vggp_ctx* ctx, const double* y, double yy, const double theta[5], int n_probes, double tol,
                                   int max_iter, double* elbo_out, double grad_out[5], vggp_info* info, void* stream);
 /* Mean read-outs of the iterative scattered step; both need only a0: mean = (s1 s2 / sigma^2) t^T a0.  VGGP_ESTATE unless the LAST
  * finished step on the context was a successful vggp_elbo_step_scattered_iter.  The POINT-WISE VARIANCES of these two come from the
- * vggp_*_var_scattered_iter entries below.
+ * vggp_*_var_scattered_iter entries below.  Multi-rank context: a0 is replicated, no collective.
  *   vggp_qv_scattered_iter         mean DEVICE [m1][m2] = L0_1 A0 L0_2^T scaled as vggp_qv_masked_iter scales it (e_d = -1 for VFF / B1)
  *   vggp_posterior_scattered_iter  xs1, xs2 DEVICE [n_star]; mean DEVICE [n_star] */
 int vggp_qv_scattered_iter(vggp_ctx* ctx, double* mean, void* stream);
@@ -267,8 +284,9 @@ int vggp_posterior_scattered_iter(vggp_ctx* ctx, const double* xs1, const double
  *   tol <= 0: 1e-10; max_iter <= 0: 100; block <= 0: the largest of 64, 32, ... with N block < 2^31 and M block < 2^31
  *   info->rounds1 = largest PCG count, info->sweeps1 = number of block solves
  * VGGP_ESTATE unless the LAST finished step on the context was a successful vggp_elbo_step_scattered_iter; VGGP_ENOCONV when a column
- * does not converge; VGGP_EINVAL on a grid plan, on paired or multi-rank contexts, for a cell outside [0, M), block > 64, null
- * arguments.  The workspace is the iterative read-outs' own: a read-out between two steps leaves the second step's bits unchanged. */
+ * does not converge; VGGP_EINVAL on a grid plan, on paired contexts, for a cell outside [0, M), block > 64, null arguments.
+ * Multi-rank context: right-hand sides and results are replicated; the operator's all-reduce of each PCG iteration is the only
+ * collective (every rank must make the same call).  The workspace is the iterative read-outs' own: a read-out between two steps leaves the second step's bits unchanged. */
 int vggp_qv_var_scattered_iter(vggp_ctx* ctx, const int64_t* cells, int64_t n_cells, double tol, int max_iter, int block, double* mean,
                                double* var, vggp_info* info, void* stream);
 int vggp_posterior_var_scattered_iter(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t n_star, double tol, int max_iter,
@@ -301,7 +319,8 @@ int vggp_kr_field2(vggp_ctx* ctx, const double* L, const double* R, const double
  *   var    DEVICE [n_cells] (NULL with n_cells = 0: the mean only)
  *   W, n_obs (masked), tol, max_iter, block: as vggp_qv_masked_iter
  * VGGP_ESTATE unless the LAST finished step on the context was the matching successful iterative step; VGGP_ENOCONV when a column does
- * not converge; VGGP_EINVAL on paired or multi-rank contexts, the wrong plan kind (a grid against VGGP_FLAG_SCATTERED), a cell index
+ * not converge; VGGP_EINVAL on paired contexts and -- the GRIDDED read-outs alone among the iterative entries -- on multi-rank contexts
+ * (the message says so; vggp_qv_*_iter and vggp_posterior_*_iter run there), the wrong plan kind (a grid against VGGP_FLAG_SCATTERED), a cell index
  * outside [0, mv1*mv2), block > 64.  The block solve's workspace is the iterative read-outs' (allocated on first use, apart from the
  * step's): a read-out leaves the kept preconditioner basis valid and the next step's results unchanged. */
 int vggp_readout_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, const double* C1, int64_t mv1, const double* C2, int64_t mv2,

@@ -188,10 +188,39 @@ int vg_allreduce(vggp_ctx* c, double* buf, long count, hipStream_t st) {
     return VGGP_OK;
 }
 
+// Does the context's collective sum over n_ranks ranks?  Asked by the iterative steps and their read-outs (masked.hip), which take host
+// decisions -- how many PCG iterations, which branch -- from all-reduced data and issue one collective per iteration: over a
+// transport that does not span the declared ranks (a callback that sums nothing, a communicator of another size) every rank would
+// count for itself and the ranks would wait for each other's collectives for ever, after computing on a fraction of the data.
+// One all-reduce of the single value 1.0, the first time an iterative entry runs on the context (every rank makes the same calls,
+// so every rank probes in the same call); the verdict is kept until the transport changes.  No-op on a single-rank context.
+int vg_comm_verify(vggp_ctx* c, const char* fn) {
+    if (c->n_ranks <= 1 && !c->comm && !c->cb) return VGGP_OK;
+    if (c->comm_probe == 0) {
+        VG_ENTER_DEVICE(c->device);
+        int rc = vg_ensure_misc(c, 256);
+        if (rc) return rc;
+        c->h_out->out[0] = 1.0;                               // (pinned; no step is in flight when an entry checks its context)
+        VG_HIP(hipMemcpyAsync(c->misc, &c->h_out->out[0], sizeof(double), hipMemcpyHostToDevice, c->own_stream));
+        if ((rc = vg_allreduce(c, reinterpret_cast<double*>(c->misc), 1, c->own_stream))) return rc;
+        VG_HIP(hipMemcpyAsync(&c->h_out->out[0], c->misc, sizeof(double), hipMemcpyDeviceToHost, c->own_stream));
+        if ((rc = vg_comm_wait(c, c->own_stream))) return rc;
+        c->comm_probe_sum = c->h_out->out[0];
+        c->comm_probe = c->comm_probe_sum == (double)c->n_ranks ? 1 : -1;
+    }
+    if (c->comm_probe < 0) {
+        vg_set_error("%s: the context's all-reduce does not sum over its n_ranks = %d ranks (1.0 from every rank came back as %g): the "
+                     "iterative entries need a transport that spans the ranks the context was created for", fn, c->n_ranks, c->comm_probe_sum);
+        return VGGP_EINVAL;
+    }
+    return VGGP_OK;
+}
+
 extern "C" int vggp_set_allreduce(vggp_ctx* c, vggp_allreduce_fn fn, void* user) {
     if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }
     c->cb = fn;
     c->cb_user = user;
+    c->comm_probe = 0;
     return VGGP_OK;
 }
 

@@ -119,6 +119,8 @@ struct vggp_ctx {
     bool comm_dead = false;           // the communicator was aborted (a peer failed or timed out): multi-rank steps return VGGP_ERCCL
     vggp_allreduce_fn cb = nullptr;   // host-callback transport (rehearsal / other transports)
     void* cb_user = nullptr;
+    int comm_probe = 0;               // vg_comm_verify: 0 not probed yet, 1 the all-reduce sums over n_ranks ranks, -1 it does not
+    double comm_probe_sum = 0.0;      // ... and what the probe of 1.0 came back as
     double* h_stage = nullptr;        // pinned staging of the callback transport
     long h_stage_count = 0;
     hipStream_t poll_stream = nullptr;   // the last step's completion was seen in the pinned result block, not through the runtime:
@@ -143,6 +145,7 @@ void vg_comm_destroy(vggp_ctx* c);
 int vg_allreduce(vggp_ctx* c, double* buf, long count, hipStream_t st);
 void vg_comm_abort(vggp_ctx* c);
 int vg_comm_wait(vggp_ctx* c, hipStream_t st, const volatile double* seq = nullptr, double want = 0.0);
+int vg_comm_verify(vggp_ctx* c, const char* fn);      // the iterative entries: VGGP_EINVAL unless the transport sums over n_ranks ranks
 // blocked dense Cholesky + inverse for matrices beyond one workgroup (masked.hip); S is destroyed; status != 0 on failure
 #define VG_DENSE_MB 128
 struct VgDenseChol { double *S, *L, *X, *DI, *Tmp, *scratch, *jit; int* status; long M; double* Sinv; };

@@ -241,7 +241,10 @@ static void vgm_layout(VgMasked& w, char* base, size_t& off) {
     w.B1s = take(m1 * n1); w.B2s = take(m2 * n2);
     w.nb1 = take(n1); w.nb2 = take(n2); w.hv1 = take(n1); w.hv2 = take(n2); w.wn1 = take(n2);
     const size_t wn2len = w.scattered ? 0 : n1;                 // (scattered: the all-reduce payload is C, C1, C2 | R3, the same
-    w.mpay = take(2 * m2 * m2 + 3 * M + wn2len + 3 * MM + 8);   //  length on every rank whatever its number of points)
+    // length on every rank whatever its number of points).  Iterative scattered step: its Gram matrices live in the payload too,
+    // G2 in the slack and G1 behind C2 (vgi_g1_offset), so that one collective carries G2 | C0, C1, C2 | G1
+    const size_t g1len = (w.iter && w.scattered) ? 32 + m1 * m1 : 0;
+    w.mpay = take(2 * m2 * m2 + 3 * M + wn2len + 3 * MM + 8 + g1len);
     w.wn2 = base ? w.mpay + 2 * m2 * m2 + 3 * M : nullptr;
     w.R3 = base ? w.wn2 + wn2len : nullptr;
     w.scal = take(32);
@@ -251,6 +254,9 @@ static void vgm_layout(VgMasked& w, char* base, size_t& off) {
     w.cholscratch = take(VG_MB * (VG_MB + 1)); w.choljit = take(8);
     w.cholstatus = reinterpret_cast<int*>(take(8));
 }
+
+// iterative scattered step: G1 sits behind [G2 | . | C0, C1, C2] in w.mpay, on a 256-byte boundary
+static size_t vgi_g1_offset(long m1, long m2) { return ((size_t)(2 * m2 * m2 + 3 * m1 * m2) + 31) & ~size_t(31); }
 
 static int vgm_prepare(vggp_ctx* c, bool iter = false) {
     VgMasked* w = reinterpret_cast<VgMasked*>(c->masked);
@@ -1275,6 +1281,47 @@ __global__ void vgi_sum_kernel(const double* part, int n, double* out, int c_fro
     out[0] = s;
 }
 
+// ---- the iterative steps on a multi-rank context ------------------------------------------------------------------------------------------
+// Split: as the dense sharded steps.  Masked grid: a rank holds the row slab Ym[rows], W[rows] and is planned with x2[rows]
+// (d2.n = its rows; n_obs, yy_obs and desc.n_total = n1 n2 are global).  Scattered points: a rank holds its own points (uneven
+// shares are fine; desc.n_total = N over all ranks, yy global).  The block vectors [m1][nbc][m2], the probes, the preconditioner,
+// its kept basis and the PCG scalars are replicated.  Three kinds of collective, all vg_allreduce on the step's stream, in the same
+// order on every rank:
+//   before the solve    ONE packed all-reduce of w.mpay: G2 | C0, C1, C2 | wn2 (masked; G1 is over the unsharded axis) or
+//                       G2 | C0, C1, C2 | G1 (scattered).  The observed fraction p of the preconditioner is the global one
+//   per PCG iteration   ONE all-reduce of the partial Phi~ Pd block (M nbc doubles) in vgi_apply -- the step's solve and every block
+//                       solve of the read-outs pass through there
+//   after the solve     ONE packed all-reduce of w.scal: the reduction jobs that are sums over this rank's rows / points (the dense
+//                       steps' local_mask; rank 0 alone contributes the replicated ones) and, behind them, ts[2 .. 9]: the five
+//                       control-variate field sums and the three exact-trace products (vgi_exact_sum is linear in Ex)
+// Invariants:
+//   1. Every host decision is taken from all-reduced or replicated data only -- the active-column count read per iteration,
+//      VGI_ESTALE / vgi_retry_stale, the cold-versus-kept choice of vgi_basis (host counters fed by iteration counts), VGGP_ENOCONV,
+//      the status words -- so all ranks take the same branch and issue the same number of collectives.  The eigen-decomposition
+//      runs redundantly on the all-reduced Gram matrices.
+//   2. Every host wait inside the iterative path is vg_comm_wait, which polls the communicator: a dead peer is an error, not a hang.
+//   (Before any of this the entries ask vg_comm_verify, once per context, whether the transport sums over n_ranks ranks at all:
+//   invariant 1 is worth nothing over one that does not, and the entry returns VGGP_EINVAL.)
+//   3. On a single-rank context nothing changes: vg_allreduce returns at once, vg_comm_wait is hipStreamSynchronize, the packing
+//      kernel is not launched, and the same kernels run in the same order on the same operands.
+#define VGI_TS_SLOT 24                            // w.scal: [RJ_COUNT reduction jobs | . | ts[2 .. 9] at VGI_TS_SLOT], 32 doubles
+static_assert(RJ_COUNT <= VGI_TS_SLOT, "the packed scalars of the iterative step overlap");
+// ts[2 .. 9] -> scal[VGI_TS_SLOT ..] (unpack = 0) and back (1): plain stores, one lane each
+__global__ void vgi_pack_ts_kernel(double* ts, double* scal, int unpack) {
+    const int k = threadIdx.x;
+    if (k >= 8) return;
+    if (unpack) ts[2 + k] = scal[VGI_TS_SLOT + k];
+    else scal[VGI_TS_SLOT + k] = ts[2 + k];
+}
+static bool vgi_multi(const vggp_ctx* c) { return c->n_ranks > 1 || c->comm || c->cb; }
+#define VGI_WAIT(c, st) do { const int wrc_ = vg_comm_wait(c, st); if (wrc_) return wrc_; } while (0)
+// the observed fraction of the preconditioner: n_obs / (grid nodes) resp. 1 / N, on a multi-rank context over ALL ranks (desc.n_total)
+static double vgi_obs_fraction(const vggp_ctx* c, bool scattered, double n_obs) {
+    const long n1 = c->desc.n1, n2 = c->desc.n2, nt = vgi_multi(c) ? c->desc.n_total : 0;
+    if (scattered) return 1.0 / (double)(nt > n1 ? nt : n1);
+    return nt > n1 * n2 ? n_obs / (double)nt : n_obs / ((double)n1 * (double)n2);
+}
+
 // Two-pass arena carver.  `layout` asks for its buffers with take() in a fixed order and is called twice: first to measure (take()
 // hands out null), then, once *mem holds that many bytes, to receive 256-byte-aligned slices of it.  *grew: the arena was too small and
 // has been replaced, so whatever it kept is gone.  oom: a format with two %.1f (GiB needed, GiB free) for the VGGP_ENOMEM raised when
@@ -1398,6 +1445,7 @@ static int vgi_apply(vggp_ctx* c, const VgMasked& w, const VgIter& it, bool fiel
         VGM_LAUNCH1D(vgi_mask_kernel, n1 * nbc * n2, st, it.F0, it.Wt, n1, nbc, n2);
         if ((rc = vgi_back(w, it, B1, it.F0, B2, it.AP, st))) return rc;
     }
+    if ((rc = vg_allreduce(c, it.AP, nb, st))) return rc;      // Phi~ Pd is a sum over this rank's rows / points (no-op on one rank)
     VGM_LAUNCH1D(vgi_axpy_rho_kernel, nb, st, it.Pd, it.AP, c->theta, nb, it.AP);
     return VGGP_OK;
 }
@@ -1431,8 +1479,8 @@ static int vgi_pcg(vggp_ctx* c, VgMasked& w, const VgIter& it, double p, double 
         hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, row, tol, it.alh, it.beh, it.nact);
         VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, m1, nbc, m2, 2);
         VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
-        VG_HIP(hipStreamSynchronize(st));
-        nact = c->h_out->counters[0][0];
+        VGI_WAIT(c, st);
+        nact = c->h_out->counters[0][0];                               // (from replicated block vectors: the same on every rank)
         iters = k + 1;
         if (stale_limit > 0 && nact > 0 && iters > stale_limit) {      // the kept basis has drifted too far: not worth iterating on
             w.ib_valid = false;
@@ -1623,11 +1671,20 @@ static void vgi_red_jobs(vggp_ctx* c, const VgMasked& w, const double* C0, VgmRe
     vgi_red_job(ra, RJ_MK2PT, d2.Mk, w.PT2, m2 * m2, 1, 1, 0);
 }
 // reductions, combine, final, copy-back and the status of the step (`what`: "masked" / "scattered", n observations with sum of squares yy)
-static int vgi_finish(vggp_ctx* c, VgMasked& w, const VgIter& it, const char* what, const VgmRedArgs& ra, double n, double yy, int iters,
-                      double* elbo_out, double grad_out[5], vggp_info* info, hipStream_t st) {
+// local_mask: the reduction jobs that are sums over this rank's rows / points.  Multi-rank: those, rank 0's copy of the replicated
+// jobs and ts[2 .. 9] travel in ONE all-reduce of w.scal before the combine kernel reads any of them
+static int vgi_finish(vggp_ctx* c, VgMasked& w, const VgIter& it, const char* what, const VgmRedArgs& ra, unsigned local_mask, double n, double yy,
+                      int iters, double* elbo_out, double grad_out[5], vggp_info* info, hipStream_t st) {
     const int n_probes = it.nbc - 1;
+    const bool multi = vgi_multi(c);
+    int rc;
     hipLaunchKernelGGL(vgm_red_kernel, dim3(VG_MD_NPART, RJ_COUNT), dim3(256), 0, st, ra);
-    hipLaunchKernelGGL(vgm_sum_kernel, dim3(1), dim3(64), 0, st, w.partial, w.scal, 0u, 1);
+    hipLaunchKernelGGL(vgm_sum_kernel, dim3(1), dim3(64), 0, st, w.partial, w.scal, local_mask, (!multi || c->rank == 0) ? 1 : 0);
+    if (multi) {
+        hipLaunchKernelGGL(vgi_pack_ts_kernel, dim3(1), dim3(64), 0, st, it.ts, w.scal, 0);
+        if ((rc = vg_allreduce(c, w.scal, 32, st))) return rc;
+        hipLaunchKernelGGL(vgi_pack_ts_kernel, dim3(1), dim3(64), 0, st, it.ts, w.scal, 1);
+    }
     hipLaunchKernelGGL(vgi_combine_kernel, dim3(1), dim3(64), 0, st, it.ts, c->theta, (double)w.M, n_probes, w.scal);
     VgmFinalArgs fa{c->theta, w.scal, w.out, n, yy, w.m1, w.m2};
     hipLaunchKernelGGL(vgm_final_kernel, dim3(1), dim3(64), 0, st, fa);
@@ -1639,7 +1696,7 @@ static int vgi_finish(vggp_ctx* c, VgMasked& w, const VgIter& it, const char* wh
         VG_HIP(hipMemcpyAsync(&c->h_out->counters[k][2], c->d[k].counters + 2, sizeof(int), hipMemcpyDeviceToHost, st));
     }
     VG_HIP(hipMemcpyAsync(&c->h_out->counters[1][3], w.cholstatus, sizeof(int), hipMemcpyDeviceToHost, st));
-    VG_HIP(hipStreamSynchronize(st));
+    VGI_WAIT(c, st);
     *elbo_out = c->h_out->out[0];
     for (int i = 0; i < 5; ++i) grad_out[i] = c->h_out->out[1 + i];
     int status = c->h_out->status[0] ? c->h_out->status[0] : (c->h_out->status[1] ? c->h_out->status[1] : 0);
@@ -1667,7 +1724,7 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     c->have_masked = false;
     c->have_iter = false;            // ... and a failed iterative step leaves nothing for vggp_qv_masked_iter / vggp_posterior_masked_iter
     VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "vggp_elbo_step_masked_iter: the context was planned for scattered points");
-    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "vggp_elbo_step_masked_iter: single-rank contexts only");
+    { const int vrc_ = vg_comm_verify(c, fn); if (vrc_) return vrc_; }
     if (n_probes <= 0) n_probes = 16;
     if (max_iter <= 0) max_iter = 100;
     if (!(tol > 0.0)) tol = 1e-10;
@@ -1691,9 +1748,12 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     double* C0 = w.mpay + 2 * m2 * m2;
     if ((rc = vgm_colstats(c, w, W, st))) return rc;
     hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, n1, n2, it.Wt);
+    // row-sharded job: G2 (H2), C0, C1, C2 and wn2 are sums over this rank's rows and lie side by side in w.mpay -- the ONE collective
+    // before the solve; G1 runs over the unsharded axis and is replicated as it is
+    if ((rc = vg_allreduce(c, w.mpay, 2 * m2 * m2 + 3 * M + n1, st))) return rc;
     bool reused = false;
     if ((rc = vgi_basis(c, w, it, c->d[0].GH, w.mpay, &reused, st))) return rc;
-    const double p = n_obs / ((double)n1 * (double)n2);
+    const double p = vgi_obs_fraction(c, false, n_obs);
     int iters = 0;
     if ((rc = vgi_step_solve(c, w, it, fn, C0, p, tol, max_iter, reused, &iters, st))) return rc;
     if ((rc = vgi_logdet(c, w, it, p, st))) return rc;
@@ -1731,7 +1791,9 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     vgi_red_job(ra, RJ_HV1, w.hv1, w.wn2, n1, 1, 1, 0);
     vgi_red_job(ra, RJ_Z2, W, w.Zb, n1 * n2, 1, 1, 3, w.Zv2);
     vgi_red_job(ra, RJ_HV2, w.hv2, w.wn1, n2, 1, 1, 0);
-    return vgi_finish(c, w, it, "masked", ra, n_obs, yy_obs, iters, elbo_out, grad_out, info, st);
+    // (the dense masked step's: wn2 is all-reduced, so the jobs over n1 and PT1 are replicated; wn1 and PT2 belong to this rank's rows)
+    const unsigned local_mask = (1u << RJ_Z1) | (1u << RJ_Z2) | (1u << RJ_HV2) | (1u << RJ_MK2PT);
+    return vgi_finish(c, w, it, "masked", ra, local_mask, n_obs, yy_obs, iters, elbo_out, grad_out, info, st);
 }
 extern "C" int vggp_elbo_step_masked_iter(vggp_ctx* c, const double* Ym, const double* W, double n_obs, double yy_obs, const double theta[5],
                                           int n_probes, double tol, int max_iter, double* elbo_out, double grad_out[5], vggp_info* info,
@@ -1842,13 +1904,18 @@ static int vgi_whitened_columns(vggp_ctx* c, const double* xs1, const double* xs
 
 // What every read-out entry checks first: the context, the data kind of its plan (not_scattered / not_grid: the entry's own words for
 // a plan of the other kind), W and n_obs of a masked step (bad_W: likewise) and the width of a block solve
-static int vgi_readout_enter(vggp_ctx* c, const char* fn, bool scattered, const char* not_scattered, const char* not_grid, const char* bad_W,
-                             const double* W, double n_obs, int block) {
+// gridded: the gridded read-outs keep to single-rank contexts (their Gram products over the data have no collective); the point-wise
+// ones run on a multi-rank context too: right-hand sides and results are replicated, the operator's all-reduce is vgi_apply's
+static int vgi_readout_enter(vggp_ctx* c, const char* fn, bool scattered, bool gridded, const char* not_scattered, const char* not_grid,
+                             const char* bad_W, const double* W, double n_obs, int block) {
     if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
     VG_NOT_PAIRED(c, fn);
     if (scattered) VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: %s", fn, not_scattered);
     else VG_REQUIRE(!(c->desc.flags & VGGP_FLAG_SCATTERED), "%s: %s", fn, not_grid);
-    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
+    if (gridded)
+        VG_REQUIRE(!vgi_multi(c), "%s: the gridded read-out of an iterative step runs on single-rank contexts only (multi-rank contexts: "
+                   "vggp_qv_*_iter / vggp_posterior_*_iter)", fn);
+    else { const int vrc_ = vg_comm_verify(c, fn); if (vrc_) return vrc_; }
     if (!scattered) VG_REQUIRE(W && std::isfinite(n_obs) && n_obs > 0.0, "%s: %s", fn, bad_W);
     VG_REQUIRE(block <= 64, "%s: block = %d exceeds 64 columns per block solve", fn, block);
     return VGGP_OK;
@@ -1874,7 +1941,7 @@ static int vgi_readout_defaults(vggp_ctx* c, const char* fn, bool scattered, int
 
 // The read-outs' arena (w.rmem) for blocks of nbc columns, the transposed mask of a masked step in it, and the step's p.
 // post: posterior(x*) needs the factor columns.  Scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N]
-static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post, const double* W, double n_obs, hipStream_t st) {
+static int vgi_readout_prepare(const vggp_ctx* c, VgMasked& w, VgReadout& r, int nbc, bool post, const double* W, double n_obs, hipStream_t st) {
     const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M, mx = std::max(m1, m2);
     VgIter& it = r.it;
     const bool sc = w.scattered;
@@ -1897,11 +1964,11 @@ static int vgi_readout_prepare(VgMasked& w, VgReadout& r, int nbc, bool post, co
         it.nact = reinterpret_cast<int*>(a.take(8));
     });
     if (rc) return rc;
+    r.p = vgi_obs_fraction(c, sc, n_obs);
     it.nbc = nbc; it.maxit = 1;
     if (!sc)
         hipLaunchKernelGGL(vgi_transpose_kernel, dim3((unsigned)((n1 + 31) / 32), (unsigned)((n2 + 31) / 32)), dim3(32, 8), 0, st, W, (long)n1, (long)n2,
                            it.Wt);
-    r.p = sc ? 1.0 / (double)n1 : n_obs / ((double)n1 * (double)n2);
     return VGGP_OK;
 }
 
@@ -1931,7 +1998,7 @@ static int vgi_solve_block(vggp_ctx* c, VgMasked& w, VgReadout& r, const char* f
 static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered, const double* W, double n_obs, const int64_t* cells,
                            const double* xs1, const double* xs2, int64_t ncols, double tol, int max_iter, int block, double* mean, double* var,
                            vggp_info* info, void* stream) {
-    int rc = vgi_readout_enter(c, fn, scattered, "plan the context with VGGP_FLAG_SCATTERED", "the context was planned for scattered points",
+    int rc = vgi_readout_enter(c, fn, scattered, /*gridded=*/false, "plan the context with VGGP_FLAG_SCATTERED", "the context was planned for scattered points",
                                "bad argument", W, n_obs, block);
     if (rc) return rc;
     const long m1 = c->desc.m1, m2 = c->desc.m2, M = m1 * m2;
@@ -1951,10 +2018,10 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered
     VgDim &d1 = c->d[0], &d2 = c->d[1];
     const int e1 = vgi_scale_exp(d1), e2 = vgi_scale_exp(d2);
     if (mode == 1 && mean && (rc = vgi_qv_mean(c, w, mean, st))) return rc;
-    if (ncols == 0) { VG_HIP(hipStreamSynchronize(st)); return VGGP_OK; }
+    if (ncols == 0) { VGI_WAIT(c, st); return VGGP_OK; }
     const int nbc = (int)std::min<int64_t>(block, ncols);
     VgReadout r;
-    if ((rc = vgi_readout_prepare(w, r, nbc, mode == 0, W, n_obs, st))) return rc;
+    if ((rc = vgi_readout_prepare(c, w, r, nbc, mode == 0, W, n_obs, st))) return rc;
     VgIter& it = r.it;
     const long nb = M * nbc;
     int max_its = 0, solves = 0;
@@ -1973,7 +2040,7 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered
                            mode == 0 ? mean + off : (double*)nullptr, var + off);
     }
     VG_HIP(hipGetLastError());
-    VG_HIP(hipStreamSynchronize(st));
+    VGI_WAIT(c, st);
     return VGGP_OK;
 }
 
@@ -2017,8 +2084,7 @@ static int vgs_check(vggp_ctx* c, const char* fn) {
     if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
     VG_NOT_PAIRED(c, fn);
     VG_REQUIRE(c->desc.flags & VGGP_FLAG_SCATTERED, "%s: plan the context with VGGP_FLAG_SCATTERED", fn);
-    VG_REQUIRE(!(c->n_ranks > 1 || c->comm || c->cb), "%s: single-rank contexts only", fn);
-    return VGGP_OK;
+    return vg_comm_verify(c, fn);
 }
 
 static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const double theta[5], int n_probes, double tol, int max_iter,
@@ -2060,12 +2126,16 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B2, B2, (int)m2, N, w.nb2);
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, V1, B1, (int)m1, N, w.hv1);
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, V2, B2, (int)m2, N, w.hv2);
-    // Gram matrices over the points
-    if ((rc = gemm_longk(B1, N, 1, B1, 1, N, d1.GH, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
-    if ((rc = gemm_longk(B2, N, 1, B2, 1, N, d2.GH, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
+    // Gram matrices over the points, in the payload beside the projections: G2 | . | C0, C1, C2 | G1
+    double *G1 = w.mpay + vgi_g1_offset(m1, m2), *G2 = w.mpay;
+    if ((rc = gemm_longk(B1, N, 1, B1, 1, N, G1, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(B2, N, 1, B2, 1, N, G2, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
+    // point-sharded job: all of them are sums over this rank's points -- the ONE collective before the solve (the gaps of the
+    // payload hold zeros on every rank)
+    if ((rc = vg_allreduce(c, w.mpay, (long)vgi_g1_offset(m1, m2) + m1 * m1, st))) return rc;
     bool reused = false;
-    if ((rc = vgi_basis(c, w, it, d1.GH, d2.GH, &reused, st))) return rc;
-    const double p = 1.0 / (double)N;
+    if ((rc = vgi_basis(c, w, it, G1, G2, &reused, st))) return rc;
+    const double p = vgi_obs_fraction(c, true, 0.0);
     int iters = 0;
     if ((rc = vgi_step_solve(c, w, it, fn, C0, p, tol, max_iter, reused, &iters, st))) return rc;
     if ((rc = vgi_logdet(c, w, it, p, st))) return rc;
@@ -2114,7 +2184,11 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     vgi_red_job(ra, RJ_HV1, w.hv1, w.nb2, N, 1, 1, 0);
     vgi_red_job(ra, RJ_Z2, w.Zb, w.Zv2, N, 1, 1, 0);
     vgi_red_job(ra, RJ_HV2, w.hv2, w.nb1, N, 1, 1, 0);
-    return vgi_finish(c, w, it, "scattered", ra, (double)N, yy, iters, elbo_out, grad_out, info, st);
+    // (the dense scattered step's: PT1, PT2 are sums over this rank's points and enter through their scalars <Mk_d, PT_d> alone)
+    const unsigned local_mask = (1u << RJ_TRPHI) | (1u << RJ_Z1) | (1u << RJ_HV1) | (1u << RJ_MK1PT) | (1u << RJ_Z2) | (1u << RJ_HV2) |
+                                (1u << RJ_MK2PT);
+    const long Ntot = (vgi_multi(c) && c->desc.n_total > N) ? c->desc.n_total : N;          // the observation count over all ranks
+    return vgi_finish(c, w, it, "scattered", ra, local_mask, (double)Ntot, yy, iters, elbo_out, grad_out, info, st);
 }
 
 extern "C" int vggp_elbo_step_scattered_iter(vggp_ctx* c, const double* y, double yy, const double theta[5], int n_probes, double tol,
@@ -2135,7 +2209,7 @@ extern "C" int vggp_qv_scattered_iter(vggp_ctx* c, double* mean, void* stream) {
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
     if ((rc = vgi_qv_mean(c, w, mean, st))) return rc;
-    VG_HIP(hipStreamSynchronize(st));
+    VGI_WAIT(c, st);
     return VGGP_OK;
 }
 
@@ -2167,7 +2241,7 @@ extern "C" int vggp_posterior_scattered_iter(vggp_ctx* c, const double* xs1, con
         VGM_LAUNCH1D(vgs_scale_mean_kernel, cn, st, mean + off, (long)cn, c->theta);
     }
     VG_HIP(hipGetLastError());
-    VG_HIP(hipStreamSynchronize(st));
+    VGI_WAIT(c, st);
     return VGGP_OK;
 }
 
@@ -2303,7 +2377,7 @@ __global__ void vgi_readout_literal_kernel(const double* S, const double* kd1, c
 static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, const double* C1, int64_t mv1,
                            const double* C2, int64_t mv2, const double* kd1, const double* kd2, const int64_t* cells, int64_t n_cells,
                            double tol, int max_iter, int block, double* mean, double* var, int flags, vggp_info* info, void* stream) {
-    int rc = vgi_readout_enter(c, fn, scattered, "the context was planned for a grid (vggp_readout_masked_iter reads those)",
+    int rc = vgi_readout_enter(c, fn, scattered, /*gridded=*/true, "the context was planned for a grid (vggp_readout_masked_iter reads those)",
                                "the context was planned for scattered points (vggp_readout_scattered_iter reads those)", "bad argument (W, n_obs)",
                                W, n_obs, block);
     if (rc) return rc;
@@ -2389,7 +2463,7 @@ static int vgi_gridded_run(vggp_ctx* c, const char* fn, bool scattered, const do
     }
     const int nbc = (int)std::min<int64_t>(block, n_cells);
     VgReadout r;
-    if ((rc = vgi_readout_prepare(w, r, nbc, false, W, n_obs, st))) return rc;
+    if ((rc = vgi_readout_prepare(c, w, r, nbc, false, W, n_obs, st))) return rc;
     const long nb = M * nbc;
     int max_its = 0, solves = 0;
     for (int64_t off = 0; off < n_cells; off += nbc) {

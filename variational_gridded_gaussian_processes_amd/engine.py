@@ -217,7 +217,8 @@ class Engine:
     def elbo_step_masked_iter(self, Ym: torch.Tensor, W: torch.Tensor, n_obs: float, yy_obs: float, theta: Sequence[float],
                               n_probes: int = 16, tol: float = 1e-10, max_iter: int = 100):
         """The masked step without any M x M matrix (PCG + Lanczos quadrature + control-variate trace estimators, fixed probes;
-        include/vggp.h): -> (elbo, grad[5], info) with info['rounds'][0] = PCG iterations."""
+        include/vggp.h): -> (elbo, grad[5], info) with info['rounds'][0] = PCG iterations.  On a multi-rank engine
+        (sharded.make_engine): Ym, W are this rank's row slab, n_obs and yy_obs the global values; every rank returns the same bits."""
         self._check_Y(Ym)
         self._check_Y(W)
         th = (C.c_double * 5)(*[float(t) for t in theta])
@@ -282,7 +283,8 @@ class Engine:
         """The scattered step without any M x M matrix or m_d^2 x N buffer (PCG on the Khatri-Rao operator, Lanczos quadrature,
         control-variate traces, fixed probes; include/vggp.h): any M with m_d <= 256.  -> (elbo, grad[5], info) with
         info['rounds'][0] = PCG iterations.  Read-outs: qv_scattered_iter, posterior_scattered_iter (means only), their
-        *_var_scattered_iter forms (with point-wise variances), readout_scattered_iter (the gridded q(v): mean and variance)."""
+        *_var_scattered_iter forms (with point-wise variances), readout_scattered_iter (the gridded q(v): mean and variance).
+        On a multi-rank engine (sharded.make_engine): y holds this rank's points (plan(..., n_total=N over all ranks)), yy is global."""
         if not (y.is_cuda and y.dtype == torch.float64 and y.is_contiguous() and y.numel() == self.n1):
             raise TypeError("y must be a contiguous float64 GPU tensor with one value per planned point")
         th = (C.c_double * 5)(*[float(t) for t in theta])

@@ -9,6 +9,16 @@ bootstraps the context: it ships the RCCL unique id from rank 0 to the other ran
 with `torch.distributed.all_reduce` on the CPU: the rehearsal of several ranks sharing ONE GPU (tests; RCCL refuses
 duplicate devices).  The reference has no multi-device path; the seam follows the sum structure
 of Kuf Kuf^T = sum over grid rows in kronecker_structure.py:249-278.
+
+The iterative steps (`Engine.elbo_step_masked_iter` on row slabs planned with x2[rows] and n_total = n1 * n2;
+`Engine.elbo_step_scattered_iter` on a rank's own points, any share, planned with scattered=True and n_total = N) and their
+point-wise read-outs (`qv_*_iter`, `posterior_*_iter`, `*_var_scattered_iter`) work unchanged on an engine from `make_engine`:
+n_obs / yy are the global values, block vectors, probes and the preconditioner are replicated, and the library issues, in the same
+order on every rank, one packed all-reduce before the solve ({G2, H2, C, C1, C2, wn2} resp. {G2, C, C1, C2, G1}), one all-reduce of
+the partial operator product (M (n_probes + 1) doubles) per PCG iteration -- the read-outs' block solves included -- and one packed
+all-reduce of 32 scalars after the solve.  Every rank returns the same code and bitwise equal results from the same call; all
+ranks must therefore make the same calls.  The first such call on a context all-reduces the value 1.0 once: a transport that does
+not sum over all n_ranks ranks (a callback that does nothing) makes the iterative entries return VGGP_EINVAL instead of hanging.  The gridded read-outs `readout_*_iter` stay single-rank (VGGP_EINVAL).
 """
 from __future__ import annotations
 
