@@ -25,6 +25,7 @@ void vg_set_error(const char* fmt, ...) {
 extern "C" const char* vggp_last_error(void) { return g_err; }
 extern "C" int vggp_version(void) { return VGGP_VERSION; }
 
+#include "arena.h"
 #include "ctx.h"
 #include "factor_elem.h"
 #define VG_CHOL_MAXJOBS_HOST 8
@@ -39,7 +40,6 @@ extern "C" int vggp_version(void) { return VGGP_VERSION; }
                                  // missed by a hair (measured: 10 log10(offdiag / thr) = 0 at every miss); the ELBO sees such elements at second order
 
 static void graphs_clear(vggp_ctx* c);
-static int vg_quiesce(vggp_ctx* c);
 
 static const char* VG_STAGE_NAMES[VGGP_NSTAGE] = {
     "factor_build", "cholesky_inverse", "trsm_BV(L^-1[A|dA|dK])", "extrap_basis(3 small gemms)", "gemm_project(S=[B2;V2]Y)",
@@ -150,20 +150,6 @@ extern "C" int vggp_destroy(vggp_ctx* c) {
     return VGGP_OK;
 }
 
-// bump allocator over the arena (256-B aligned)
-struct Bump {
-    char* base;
-    size_t off = 0;
-    bool dry;
-    template <typename T>
-    T* take(size_t count) {
-        off = (off + 255) & ~size_t(255);
-        T* p = dry ? nullptr : reinterpret_cast<T*>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 static int pick_split(int tiles, int K, int target) {
     int s = (target + tiles - 1) / tiles;
     int maxs = std::max(1, K / (4 * VG_BK));
@@ -176,11 +162,7 @@ static long vg_grid_len(int basis, long m) {
     if (basis == VGGP_BASIS_VFF) return 2 + (m - 1) / 2 + 1;  // a, b, omega_0 .. omega_M (m = 2M + 1)
     return m;                                                 // points / B1 knots / trivial
 }
-// +1: Kuu_d = s_d K0, Kuf_d = s_d A0 (kernel-evaluated bases);  -1: Kuu_d = K0 / s_d, Kuf_d = A0 (inter-domain VFF / B1).
-// B = L^{-1} Kuf is sqrt(s) L0^{-1} A0 either way, so only u-space results (q(v)) need the sign.
-static int vg_uexp(int basis) { return (basis == VGGP_BASIS_VFF || basis == VGGP_BASIS_B1) ? -1 : 1; }
-
-static void layout(vggp_ctx* c, Bump& b) {
+static void layout(vggp_ctx* c, VgArena& b) {
     // Allocation ORDER matters: the small kernels of a step are latency chains whose first loads miss everything
     // (the producer ran on another XCD), and each distinct 2 MB region they touch adds an address-translation miss on
     // top.  So the arrays are grouped by the stage that reads them -- tail (m-space) arrays together, eigen-stage arrays
@@ -361,17 +343,8 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
     c->d[1] = VgDim();
     c->d[0].kind = desc->kind1; c->d[0].basis = desc->basis1; c->d[0].n = (int)desc->n1; c->d[0].m = (int)desc->m1;
     c->d[1].kind = desc->kind2; c->d[1].basis = desc->basis2; c->d[1].n = (int)desc->n2; c->d[1].m = (int)desc->m2;
-    Bump dry{nullptr, 0, true};
-    layout(c, dry);
-    const size_t need = dry.off + 4096;
-    if (need > c->arena_bytes) {
-        if (c->arena) { VG_HIP(hipFree(c->arena)); c->arena = nullptr; c->arena_bytes = 0; }
-        VG_HIP(hipMalloc(&c->arena, need));
-        c->arena_bytes = need;
-    }
-    Bump wet{reinterpret_cast<char*>(c->arena), 0, false};
-    layout(c, wet);
-    c->arena_used = wet.off;
+    bool grew = false;      // (grow-only; the whole used part is cleared: "unused slots stay zero")
+    if ((rc = vg_arena_carve(&c->arena, &c->arena_bytes, nullptr, &grew, [&](VgArena& a) { layout(c, a); }, &c->arena_used))) return rc;
     VG_HIP(hipMemset(c->arena, 0, c->arena_used));
     const double one = 1.0;
     for (int k = 0; k < 2; ++k) {
@@ -1456,7 +1429,7 @@ static int set_theta(vggp_ctx* c, const double theta[5]) {
 // returns only after the end-of-graph bookkeeping of the runtime (measured: ~8 us later); the stream itself keeps the order of
 // whatever is enqueued next.  Anything that must not overlap with the tail of the graph (destroying a graph exec, re-planning)
 // calls vg_quiesce first.  Falls back to the real synchronisation after 20 ms (a fault would otherwise spin for ever).
-static int vg_quiesce(vggp_ctx* c) {
+int vg_quiesce(vggp_ctx* c) {
     if (c->poll_stream_valid) { c->poll_stream_valid = false; VG_HIP(hipStreamSynchronize(c->poll_stream)); }
     return VGGP_OK;
 }

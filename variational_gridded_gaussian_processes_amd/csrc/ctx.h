@@ -139,7 +139,13 @@ struct vggp_ctx {
 };
 
 
+// +1: Kuu_d = s_d K0, Kuf_d = s_d A0 (kernel-evaluated bases);  -1: Kuu_d = K0 / s_d, Kuf_d = A0 (inter-domain VFF / B1).
+// B = L^{-1} Kuf is sqrt(s) L0^{-1} A0 either way, so only u-space results (q(v)) need the sign.
+static inline int vg_uexp(int basis) { return (basis == VGGP_BASIS_VFF || basis == VGGP_BASIS_B1) ? -1 : 1; }
+
 int vg_ensure_misc(vggp_ctx* c, size_t bytes);
+// a step whose completion was only seen in its pinned block may still be finishing on its stream: wait for that stream (api.hip)
+int vg_quiesce(vggp_ctx* c);
 int vg_comm_init(vggp_ctx* c, int n_ranks, int rank, const void* unique_id);
 void vg_comm_destroy(vggp_ctx* c);
 int vg_allreduce(vggp_ctx* c, double* buf, long count, hipStream_t st);

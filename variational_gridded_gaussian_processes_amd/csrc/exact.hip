@@ -12,6 +12,7 @@
 // s kd1 kd2 + (F o F) 1 / v (the reference's :177-191, since P^-1 = Kxx^-1 + I / v for P = Kxx - Kxx Sigma^-1 Kxx).
 // The workspace hangs off the context (c->exact) and shares nothing with a vggp_plan: either may be replaced without the other noticing.
 // Specification: tests/exact_gp_spec.py.
+#include "arena.h"
 #include "gen_gemm.h"
 
 #include <algorithm>
@@ -139,20 +140,14 @@ struct VgExact {
     double theta[5] = {0, 0, 0, 0, 0}, eps = 0.0;
 };
 
-static void ex_layout(VgExact& w, char* base, size_t& off) {
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~size_t(255);
-        double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return p;
-    };
+static void ex_layout(VgExact& w, VgArena& a) {
     const size_t N = w.N, NN = N * N;
-    w.x1 = take(N); w.x2 = take(N);
-    w.S = take(NN); w.L = take(NN); w.X = take(NN); w.Sinv = take(NN);
-    w.DI = take((size_t)w.nblk * PZ_MB * PZ_MB); w.Tmp = take((size_t)PZ_MB * N);
-    w.cholscratch = take(PZ_MB * (PZ_MB + 1)); w.jit = take(8);
-    w.status = reinterpret_cast<int*>(take(8));
-    w.wv = take(N); w.alpha = take(N); w.part = take((size_t)w.ntile * 4); w.out = take(8);
+    w.x1 = a.take(N); w.x2 = a.take(N);
+    w.S = a.take(NN); w.L = a.take(NN); w.X = a.take(NN); w.Sinv = a.take(NN);
+    w.DI = a.take((size_t)w.nblk * PZ_MB * PZ_MB); w.Tmp = a.take((size_t)PZ_MB * N);
+    w.cholscratch = a.take(PZ_MB * (PZ_MB + 1)); w.jit = a.take(8);
+    w.status = reinterpret_cast<int*>(a.take(8));
+    w.wv = a.take(N); w.alpha = a.take(N); w.part = a.take((size_t)w.ntile * 4); w.out = a.take(8);
 }
 
 void vg_exact_free(vggp_ctx* c) {
@@ -165,12 +160,6 @@ void vg_exact_free(vggp_ctx* c) {
 }
 
 static VgExact* ex_ws(vggp_ctx* c) { return reinterpret_cast<VgExact*>(c->exact); }
-
-// a step of the planned model whose completion was only seen in its pinned block may still be finishing on its stream
-static int ex_quiesce(vggp_ctx* c) {
-    if (c->poll_stream_valid) { c->poll_stream_valid = false; VG_HIP(hipStreamSynchronize(c->poll_stream)); }
-    return VGGP_OK;
-}
 
 static int ex_gemv(const double* A, long sa_m, long sa_k, const double* x, double* y, int M, int K, hipStream_t st) {
     VgGemmBatch g;
@@ -194,27 +183,20 @@ extern "C" int vggp_exact_plan(vggp_ctx* c, int kind1, int kind2, const double* 
     tmp.nblk = (int)((N + PZ_MB - 1) / PZ_MB);
     tmp.tiles = (int)((N + EX_GT - 1) / EX_GT);
     tmp.ntile = tmp.tiles * (tmp.tiles + 1) / 2;
-    size_t off = 0;
-    ex_layout(tmp, nullptr, off);
-    const size_t bytes = off + 4096;
+    const size_t bytes = vg_arena_measure([&](VgArena& a) { ex_layout(tmp, a); });
     int rc;
-    if ((rc = ex_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     if (c->exact) { VG_HIP(hipDeviceSynchronize()); vg_exact_free(c); }      // (the earlier exact plan: its read-outs may be in flight)
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b) {
-            vg_set_error("vggp_exact_plan: the exact GP (N = %lld) needs %.1f GiB of workspace, %.1f GiB are free", (long long)N,
-                         (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
-            return VGGP_ENOMEM;
-        }
+    size_t free_b = 0;
+    if (!vg_arena_fits(bytes, &free_b)) {
+        vg_set_error("vggp_exact_plan: the exact GP (N = %lld) needs %.1f GiB of workspace, %.1f GiB are free", (long long)N,
+                     (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
+        return VGGP_ENOMEM;
     }
     VgExact* w = new VgExact(tmp);
     c->exact = w;                        // owned by the context from here on (vg_exact_free releases it on any later failure)
     VG_HIP(hipHostMalloc((void**)&w->host, sizeof(ExHost), hipHostMallocDefault));
-    VG_HIP(hipMalloc(&w->mem, bytes));
-    VG_HIP(hipMemset(w->mem, 0, bytes));
-    off = 0;
-    ex_layout(*w, reinterpret_cast<char*>(w->mem), off);
+    if ((rc = vg_arena_alloc(&w->mem, bytes, [&](VgArena& a) { ex_layout(*w, a); }))) return rc;
     VG_HIP(hipMemcpy(w->x1, x1, sizeof(double) * N, hipMemcpyHostToDevice));
     VG_HIP(hipMemcpy(w->x2, x2, sizeof(double) * N, hipMemcpyHostToDevice));
     return VGGP_OK;
@@ -266,7 +248,7 @@ extern "C" int vggp_exact_step(vggp_ctx* c, const double* y, const double theta[
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     int rc;
-    if ((rc = ex_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     int failed = 0;
     rc = pz_jitter_retry(&w.eps, &failed, [&](bool) {
         c->nev = 0;
@@ -335,7 +317,7 @@ extern "C" int vggp_exact_posterior(vggp_ctx* c, const double* xs1, const double
     if (ns == 0) return VGGP_OK;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    if ((rc = ex_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     const double s = w.theta[2] * w.theta[3];
     const PzPts g{w.x1, w.x2, xs1, xs2, w.kind1, w.kind2, 1.0 / w.theta[0], 1.0 / w.theta[1]};
     hipLaunchKernelGGL(pz_mean_kernel<PzPts>, dim3((unsigned)ns), dim3(256), 0, st, g, w.alpha, (int)w.N, s, mean);
@@ -357,7 +339,7 @@ extern "C" int vggp_exact_posterior_cov(vggp_ctx* c, const double* xs1, const do
     VG_REQUIRE(xs1 && xs2 && cov, "vggp_exact_posterior_cov: null argument");
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    if ((rc = ex_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     const int N = (int)w.N;
     const double s = w.theta[2] * w.theta[3], inv1 = 1.0 / w.theta[0], inv2 = 1.0 / w.theta[1];
     if ((rc = vg_ensure_misc(c, sizeof(double) * (2 * (size_t)N * ns + 64)))) return rc;
@@ -390,7 +372,7 @@ extern "C" int vggp_exact_readout(vggp_ctx* c, const double* C1, int64_t mv1, co
     const long nv = mv1 * mv2;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    if ((rc = ex_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     const int N = (int)w.N;
     const double s = w.theta[2] * w.theta[3], v = w.theta[4];
     const PzFace f{C1, C2, (int)mv2, N};

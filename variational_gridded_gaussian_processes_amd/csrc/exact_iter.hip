@@ -9,6 +9,8 @@
 // mode) and feeds all of them from one generated fragment.
 // Every product of two kernels is a polynomial in a = |d1| / ell1, b = |d2| / ell2 times ONE exp of the summed exponents, and both
 // length-scale derivatives share it; the kernel kinds are template parameters (dispatch per launch, nothing per element).
+#include "arena.h"
+#include "block_pcg.h"
 #include "ctx.h"
 #include "lanczos_quad.h"
 
@@ -174,8 +176,8 @@ extern "C" int vggp_exact_kmv(vggp_ctx* c, int kind1, int kind2, double ell1, do
 //         Lz Lz^T = s K0[idx, idx] (psd_safe jitter schedule, info.jitter1),  L = s K0[:, idx] Lz^-T,  P = v I + L L^T,
 //         L^T L = V diag(lam) V^T (vggp_eigh; lam_i <= 1e-14 lam_max dropped),  Q = L V lam^-1/2,
 //         P^w = v^w (I + Q diag((1 + lam / v)^w - 1) Q^T) for w = -1, 1/2,  log|P| = N log v + sum log1p(lam / v).
-//     Block PCG on [y, z_1 .. z_p], z_c = P^1/2 z0_c (z0: vgi_probe_kernel's counter hash keyed on (c, i)); per-column scalars and
-//     stopping rule of vgi_pcg_scalars_kernel; log|Sigma| = log|P| + mean_c N e1^T log(T_c) e1 from the PCG coefficients (the small
+//     Block PCG on [y, z_1 .. z_p], z_c = P^1/2 z0_c (z0: vg_pcg_probe_kernel's counter hash keyed on (c, i)); the loop, the per-column
+//     scalars and the stopping rule are vg_block_pcg's (block_pcg.h); log|Sigma| = log|P| + mean_c N e1^T log(T_c) e1 from the PCG coefficients (the small
 //     tridiagonal eigenproblems run on the host: k <= max_iter unknowns per probe); traces mean_c u_c^T D w_c with ONE derivative-mode
 //     product on [alpha, w_1 .. w_p].  Block vectors are [N][nbp], nbp = 16 ceil(nb / 16), zero-padded.  Every sum over the points is
 //     taken per 512-row chunk and the chunk partials are added in ascending order: bitwise repeatable.
@@ -197,7 +199,7 @@ struct VgExactIter {
     double *x1 = nullptr, *x2 = nullptr, *alpha = nullptr;   // [N]
     double *X = nullptr, *R = nullptr, *Pd = nullptr, *AP = nullptr, *Zp = nullptr, *Wz = nullptr, *Bk = nullptr;   // [N][64]
     double *part = nullptr;                                  // [nchunk][2][64]
-    double *col = nullptr;                                   // [8][64] PCG scalars (rows as vgi_pcg_scalars_kernel) + [4][64] sums
+    double *col = nullptr;                                   // [8][64] PCG scalars (rows as vg_pcg_scalars_kernel) + [4][64] sums
     double *T = nullptr;                                     // [256][64]
     double *zx1 = nullptr, *zx2 = nullptr, *lam = nullptr, *cf = nullptr;   // [256] landmarks, eigenvalues; [3][256] coefficients
     double *Kzz = nullptr, *Lz = nullptr, *Lzi = nullptr, *G = nullptr, *Vt = nullptr;   // [256][256]
@@ -214,22 +216,16 @@ struct VgExactIter {
     int rq = 0;                                              // columns of Q (0: P = v I)
 };
 
-static void exi_layout(VgExactIter& w, char* base, size_t& off) {
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~size_t(255);
-        double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return p;
-    };
+static void exi_layout(VgExactIter& w, VgArena& a) {
     const size_t N = w.N, R2 = (size_t)EXI_MAX_RANK * EXI_MAX_RANK;
-    w.x1 = take(N); w.x2 = take(N); w.alpha = take(N);
-    w.X = take(N * 64); w.R = take(N * 64); w.Pd = take(N * 64); w.AP = take(N * 64); w.Zp = take(N * 64); w.Wz = take(N * 64);
-    w.Bk = take(N * 64);
-    w.part = take((size_t)w.nchunk * 128); w.col = take(12 * 64); w.T = take((size_t)EXI_MAX_RANK * 64);
-    w.zx1 = take(EXI_MAX_RANK); w.zx2 = take(EXI_MAX_RANK); w.lam = take(EXI_MAX_RANK); w.cf = take(3 * EXI_MAX_RANK);
-    w.Kzz = take(R2); w.Lz = take(R2); w.Lzi = take(R2); w.G = take(R2); w.Vt = take(R2);
-    w.cells = reinterpret_cast<long long*>(take(64));
-    w.nact = reinterpret_cast<int*>(take(8));
+    w.x1 = a.take(N); w.x2 = a.take(N); w.alpha = a.take(N);
+    w.X = a.take(N * 64); w.R = a.take(N * 64); w.Pd = a.take(N * 64); w.AP = a.take(N * 64); w.Zp = a.take(N * 64); w.Wz = a.take(N * 64);
+    w.Bk = a.take(N * 64);
+    w.part = a.take((size_t)w.nchunk * 128); w.col = a.take(12 * 64); w.T = a.take((size_t)EXI_MAX_RANK * 64);
+    w.zx1 = a.take(EXI_MAX_RANK); w.zx2 = a.take(EXI_MAX_RANK); w.lam = a.take(EXI_MAX_RANK); w.cf = a.take(3 * EXI_MAX_RANK);
+    w.Kzz = a.take(R2); w.Lz = a.take(R2); w.Lzi = a.take(R2); w.G = a.take(R2); w.Vt = a.take(R2);
+    w.cells = reinterpret_cast<long long*>(a.take(64));
+    w.nact = reinterpret_cast<int*>(a.take(8));
 }
 
 static VgExactIter* exi_ws(vggp_ctx* c) { return reinterpret_cast<VgExactIter*>(c->exact_iter); }
@@ -246,10 +242,6 @@ void vg_exact_iter_free(vggp_ctx* c) {
     c->exact_iter = nullptr;
 }
 
-static int exi_quiesce(vggp_ctx* c) {
-    if (c->poll_stream_valid) { c->poll_stream_valid = false; VG_HIP(hipStreamSynchronize(c->poll_stream)); }
-    return VGGP_OK;
-}
 // grow-only side buffers (the device is idle when one is replaced)
 static int exi_grow(void** buf, size_t bytes) {
     if (*buf) { VG_HIP(hipDeviceSynchronize()); VG_HIP(hipFree(*buf)); *buf = nullptr; }
@@ -266,12 +258,6 @@ static int exi_need_scr(VgExactIter& w, size_t n) {
 }
 
 // ---- small kernels -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long exi_mix(unsigned long long x) {       // splitmix64 finaliser (vgi_mix)
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
 // one kernel element with the kinds as run-time arguments (landmark block, explicit right-hand sides: O(N r) elements, not N^2)
 __device__ __forceinline__ double exi_k0(int kind1, int kind2, double d1, double d2, double inv1, double inv2) {
     double p1, q1, g1, p2, q2, g2;
@@ -293,15 +279,6 @@ __device__ __forceinline__ double exi_k0(int kind1, int kind2, double d1, double
 #define EXI_LAUNCH1D(kern, n, st, ...) \
     hipLaunchKernelGGL(kern, dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, st, __VA_ARGS__)
 
-// blk[i][c] = +-1 for the probe columns 1 <= c < nbc, 0 elsewhere
-__global__ void exi_probe_kernel(double* blk, long N, int nbp, int nbc, unsigned long long seed) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * nbp) return;
-    const long i = idx / nbp;
-    const int c = (int)(idx - i * nbp);
-    const unsigned long long h = exi_mix(seed ^ exi_mix(((unsigned long long)c << 40) ^ (unsigned long long)i));
-    blk[idx] = (c == 0 || c >= nbc) ? 0.0 : ((h >> 17) & 1ULL ? 1.0 : -1.0);
-}
 // dst[i * ldd] = src[i * lds]
 __global__ void exi_copycol_kernel(const double* src, long lds, double* dst, long ldd, long N) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -356,46 +333,6 @@ __global__ __launch_bounds__(256) void exi_coldots_kernel(const double* A, long 
         const int q = threadIdx.x >> 6;
         part[((long)blockIdx.x * 2 + q) * 64 + cidx] = (sh[q][0][cidx] + sh[q][1][cidx]) + (sh[q][2][cidx] + sh[q][3][cidx]);
     }
-}
-// chunk partials -> column sums (ascending chunk order), then the PCG scalar logic of vgi_pcg_scalars_kernel, one lane per column.
-// col rows: [0] rz, [1] pAp, [2] r0^2, [3] rr, [4] alpha, [5] beta, [6] active, [7] k.  phase 3: plain sums into rows [8], [9].
-__global__ void exi_scalars_kernel(const double* part, int nchunk, double* col, int ncols, int phase, int it, double tol, double* alh,
-                                   double* beh, int* nact) {
-    const int c = threadIdx.x;
-    double *rz = col, *pAp = col + 64, *r02 = col + 128, *rr = col + 192, *al = col + 256, *be = col + 320, *act = col + 384, *kc = col + 448;
-    if (c < 64) {
-        double s0 = 0.0, s1 = 0.0;
-        for (int k = 0; k < nchunk; ++k) { s0 += part[((long)k * 2) * 64 + c]; s1 += part[((long)k * 2 + 1) * 64 + c]; }
-        if (phase == 0) {
-            rz[c] = s0; rr[c] = s1; r02[c] = s1; act[c] = (c < ncols && s1 > 0.0) ? 1.0 : 0.0; kc[c] = 0.0; al[c] = 0.0; be[c] = 0.0;
-        } else if (phase == 1) {
-            pAp[c] = s0;
-            const double a = (act[c] != 0.0 && s0 > 0.0) ? rz[c] / s0 : 0.0;
-            al[c] = a;
-            if (alh) alh[(long)it * 64 + c] = a;
-        } else if (phase == 2) {
-            rr[c] = s1;
-            const double b = (act[c] != 0.0 && rz[c] > 0.0) ? s0 / rz[c] : 0.0;
-            be[c] = b;
-            if (beh) beh[(long)it * 64 + c] = b;
-            rz[c] = s0;
-            if (act[c] != 0.0) kc[c] += 1.0;
-            if (!(s1 > tol * tol * r02[c])) act[c] = 0.0;
-        } else {
-            col[512 + c] = s0; col[576 + c] = s1;
-        }
-    }
-    __syncthreads();
-    if ((phase == 0 || phase == 2) && threadIdx.x == 0) { int n = 0; for (int k = 0; k < 64; ++k) n += act[k] != 0.0 ? 1 : 0; *nact = n; }
-}
-// phase 1: x += alpha_c p, r -= alpha_c ap;  phase 2: p = z + beta_c p
-__global__ void exi_update_kernel(double* X, double* R, double* Pd, const double* AP, const double* Zp, const double* col, long n, int nbp,
-                                  int phase) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n) return;
-    const int c = (int)(idx % nbp);
-    if (phase == 1) { const double a = col[256 + c]; X[idx] += a * Pd[idx]; R[idx] -= a * AP[idx]; }
-    else Pd[idx] = Zp[idx] + col[320 + c] * Pd[idx];
 }
 // R[i][c] = s C1[a_c][i] C2[b_c][i] for the listed cells (c < cn), 0 in the unused columns
 __global__ void exi_cellrhs_kernel(const double* C1, const double* C2, const long long* cells, int cn, long mv2, long N, double s, double* R) {
@@ -477,48 +414,46 @@ static int exi_apply_p(VgExactIter& w, const double* in, double* out, int nbp, i
     VG_HIP(hipGetLastError());
     return VGGP_OK;
 }
-static int exi_dots(VgExactIter& w, const double* A, long lda, const double* B, long ldb, const double* Cc, long ldc, const double* D, long ldd,
-                    int ncols, int phase, int it, double tol, bool hist, hipStream_t st) {
+static void exi_coldots(VgExactIter& w, const double* A, long lda, const double* B, long ldb, const double* Cc, long ldc, const double* D, long ldd,
+                        int ncols, hipStream_t st) {
     hipLaunchKernelGGL(exi_coldots_kernel, dim3((unsigned)w.nchunk), dim3(256), 0, st, A, lda, B, ldb, Cc, ldc, D, ldd, w.N, ncols, w.part);
-    hipLaunchKernelGGL(exi_scalars_kernel, dim3(1), dim3(64), 0, st, w.part, w.nchunk, w.col, ncols, phase, it, tol, hist ? w.alh : nullptr,
-                       hist ? w.beh : nullptr, w.nact);
+}
+// plain column sums <A, B>_c, <C, D>_c (C optional) into rows [8], [9] of w.col
+static int exi_sums(VgExactIter& w, const double* A, long lda, const double* B, long ldb, const double* Cc, long ldc, const double* D, long ldd,
+                    int ncols, hipStream_t st) {
+    exi_coldots(w, A, lda, B, ldb, Cc, ldc, D, ldd, ncols, st);
+    hipLaunchKernelGGL(vg_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, w.part, w.nchunk, w.col, 64, ncols, 3, 0, 0.0, (double*)nullptr,
+                       (double*)nullptr, w.nact);
     VG_HIP(hipGetLastError());
     return VGGP_OK;
 }
-static int exi_read_nact(VgExactIter& w, hipStream_t st, int* nact) {
-    VG_HIP(hipMemcpyAsync(&w.host->nact, w.nact, sizeof(int), hipMemcpyDeviceToHost, st));
-    VG_HIP(hipStreamSynchronize(st));
-    *nact = w.host->nact;
-    return VGGP_OK;
-}
-// Block PCG on Sigma X = R (R holds the right-hand sides on entry, [N][nbp], ncols of them), preconditioner P^-1.
+// Block PCG on Sigma X = R (vg_block_pcg, block_pcg.h; R holds the right-hand sides on entry, [N][nbp], ncols of them).  The caller
+// object: the operator is ONE matrix-free product Sigma p = s K0 p + v p, the preconditioner P^-1 of exi_apply_p, a column dot is the
+// sum of 512-row chunk partials in ascending order, and the host waits with a stream sync on the workspace's own pinned word
+// (single-rank only).  The active count is read after the start too: an all-zero block reports zero iterations.
 static int exi_pcg(VgExactIter& w, int nbp, int ncols, double tol, int max_iter, bool hist, int* iters, int* nact_out, hipStream_t st) {
-    const long n = w.N * nbp;
-    const double s = w.theta[2] * w.theta[3], v = w.theta[4];
-    int rc, nact = 0, it = 0;
-    VG_HIP(hipMemsetAsync(w.X, 0, sizeof(double) * n, st));
-    if ((rc = exi_apply_p(w, w.R, w.Zp, nbp, 0, st))) return rc;
-    VG_HIP(hipMemcpyAsync(w.Pd, w.Zp, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    if ((rc = exi_dots(w, w.R, nbp, w.Zp, nbp, w.R, nbp, w.R, nbp, ncols, 0, 0, tol, hist, st))) return rc;
-    if ((rc = exi_read_nact(w, st, &nact))) return rc;
-    while (nact > 0 && it < max_iter) {
-        VG_HIP(exi_kmv_self(w, w.Pd, nbp, nbp, w.AP, nullptr, nullptr, s, w.Pd, v, st));                // AP = s K0 p + v p
-        if ((rc = exi_dots(w, w.Pd, nbp, w.AP, nbp, nullptr, 0, nullptr, 0, ncols, 1, it, tol, hist, st))) return rc;
-        EXI_LAUNCH1D(exi_update_kernel, n, st, w.X, w.R, w.Pd, w.AP, w.Zp, w.col, n, nbp, 1);
-        if ((rc = exi_apply_p(w, w.R, w.Zp, nbp, 0, st))) return rc;
-        if ((rc = exi_dots(w, w.R, nbp, w.Zp, nbp, w.R, nbp, w.R, nbp, ncols, 2, it, tol, hist, st))) return rc;
-        EXI_LAUNCH1D(exi_update_kernel, n, st, w.X, w.R, w.Pd, w.AP, w.Zp, w.col, n, nbp, 2);
-        VG_HIP(hipGetLastError());
-        ++it;
-        if ((rc = exi_read_nact(w, st, &nact))) return rc;
-    }
-    *iters = it;
-    *nact_out = nact;
-    return VGGP_OK;
-}
-// e1^T log(T) e1 of the k x k Lanczos tridiagonal (lanczos_quad.h: the routine of vgi_slq_kernel); false: the quadrature failed
-static bool exi_slq(std::vector<double>& d, std::vector<double>& e, std::vector<double>& z, int k, double* out) {
-    return vg_lanczos_logquad(d.data(), e.data(), z.data(), k, out) == 0;
+    struct Ops {
+        VgExactIter& w; int nbp, ncols; hipStream_t st;
+        int apply() {                                                   // AP = s K0 p + v p
+            VG_HIP(exi_kmv_self(w, w.Pd, nbp, nbp, w.AP, nullptr, nullptr, w.theta[2] * w.theta[3], w.Pd, w.theta[4], st));
+            return VGGP_OK;
+        }
+        int precond() { return exi_apply_p(w, w.R, w.Zp, nbp, 0, st); }
+        int dots(int phase) {
+            if (phase == 1) exi_coldots(w, w.Pd, nbp, w.AP, nbp, nullptr, 0, nullptr, 0, ncols, st);
+            else exi_coldots(w, w.R, nbp, w.Zp, nbp, w.R, nbp, w.R, nbp, ncols, st);
+            return VGGP_OK;
+        }
+        int active(int* nact) {
+            VG_HIP(hipMemcpyAsync(&w.host->nact, w.nact, sizeof(int), hipMemcpyDeviceToHost, st));
+            VG_HIP(hipStreamSynchronize(st));
+            *nact = w.host->nact;
+            return VGGP_OK;
+        }
+    };
+    const VgBlockPcg b{w.X, w.R, w.Pd, w.AP, w.Zp, w.part, w.nchunk, w.col, 64, hist ? w.alh : nullptr, hist ? w.beh : nullptr, w.nact,
+                       w.N, nbp, 1, ncols, /*count_at_start=*/true};
+    return vg_block_pcg(b, Ops{w, nbp, ncols, st}, tol, max_iter, hist, /*stale_limit=*/0, iters, nact_out, st);
 }
 
 static void exi_fill_info(vggp_info* info, double jit, int sweeps, int rounds, int status) {
@@ -540,19 +475,15 @@ extern "C" int vggp_exact_iter_plan(vggp_ctx* c, int kind1, int kind2, const dou
     VgExactIter tmp;
     tmp.N = N; tmp.kind1 = kind1; tmp.kind2 = kind2;
     tmp.nchunk = (int)((N + EXI_CHUNK - 1) / EXI_CHUNK);
-    size_t off = 0;
-    exi_layout(tmp, nullptr, off);
-    const size_t bytes = off + 4096;
+    const size_t bytes = vg_arena_measure([&](VgArena& a) { exi_layout(tmp, a); });
     int rc;
-    if ((rc = exi_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     if (c->exact_iter) { VG_HIP(hipDeviceSynchronize()); vg_exact_iter_free(c); }
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b) {
-            vg_set_error("vggp_exact_iter_plan: the iterative exact GP (N = %lld) needs %.1f GiB of workspace, %.1f GiB are free", (long long)N,
-                         (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
-            return VGGP_ENOMEM;
-        }
+    size_t free_b = 0;
+    if (!vg_arena_fits(bytes, &free_b)) {
+        vg_set_error("vggp_exact_iter_plan: the iterative exact GP (N = %lld) needs %.1f GiB of workspace, %.1f GiB are free", (long long)N,
+                     (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
+        return VGGP_ENOMEM;
     }
     VgExactIter* w = new VgExactIter(tmp);
     c->exact_iter = w;                   // owned by the context from here on
@@ -563,9 +494,7 @@ extern "C" int vggp_exact_iter_plan(vggp_ctx* c, int kind1, int kind2, const dou
         vg_set_error("vggp_exact_iter_plan: out of memory (%.1f GiB of workspace for N = %lld)", (double)bytes / 1073741824.0, (long long)N);
         return VGGP_ENOMEM;
     }
-    VG_HIP(hipMemset(w->mem, 0, bytes));
-    off = 0;
-    exi_layout(*w, reinterpret_cast<char*>(w->mem), off);
+    if ((rc = vg_arena_place(w->mem, bytes, [&](VgArena& a) { exi_layout(*w, a); }))) return rc;
     VG_HIP(hipMemcpy(w->x1, x1, sizeof(double) * N, hipMemcpyHostToDevice));
     VG_HIP(hipMemcpy(w->x2, x2, sizeof(double) * N, hipMemcpyHostToDevice));
     return VGGP_OK;
@@ -656,7 +585,7 @@ extern "C" int vggp_exact_step_iter(vggp_ctx* c, const double* y, const double t
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     int rc;
-    if ((rc = exi_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     const long N = w.N;
     const int nbc = 1 + n_probes, nbp = 16 * ((nbc + 15) / 16);
     const long n = N * nbp;
@@ -672,7 +601,7 @@ extern "C" int vggp_exact_step_iter(vggp_ctx* c, const double* y, const double t
     rc = exi_precond(c, w, rank, &jit, &logdetP, st);
     if (rc) { exi_fill_info(info, rc == VGGP_ENOTPD ? -1.0 : jit, n_probes, 0, rc); return rc; }
     // right-hand sides: column 0 = y, columns c >= 1 = P^1/2 z0_c;  Wz = P^-1 of them
-    EXI_LAUNCH1D(exi_probe_kernel, n, st, w.Bk, N, nbp, nbc, 0x5647475000000001ULL);
+    EXI_LAUNCH1D(vg_pcg_probe_kernel, n, st, w.Bk, N, nbp, 1, nbc, 0x5647475000000001ULL);
     VG_HIP(hipGetLastError());
     if ((rc = exi_apply_p(w, w.Bk, w.R, nbp, 1, st))) return rc;
     if ((rc = exi_apply_p(w, w.R, w.Wz, nbp, 0, st))) return rc;
@@ -691,16 +620,16 @@ extern "C" int vggp_exact_step_iter(vggp_ctx* c, const double* y, const double t
     VG_HIP(hipGetLastError());
     VG_HIP(exi_kmv_self(w, w.Wz, nbc, nbp, w.AP, w.Zp, w.Pd, 1.0, nullptr, 0.0, st));
     std::vector<double> hcol(12 * 64), dK(64), d1(64), d2(64), dI(64);
-    if ((rc = exi_dots(w, w.X, nbp, w.AP, nbp, w.X, nbp, w.Zp, nbp, nbc, 3, 0, tol, false, st))) return rc;
+    if ((rc = exi_sums(w, w.X, nbp, w.AP, nbp, w.X, nbp, w.Zp, nbp, nbc, st))) return rc;
     VG_HIP(hipMemcpyAsync(hcol.data(), w.col, sizeof(double) * 12 * 64, hipMemcpyDeviceToHost, st));
     VG_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < 64; ++k) { dK[k] = hcol[512 + k]; d1[k] = hcol[576 + k]; }
     const std::vector<double> kc(hcol.begin() + 448, hcol.begin() + 512);
-    if ((rc = exi_dots(w, w.X, nbp, w.Pd, nbp, w.X, nbp, w.Wz, nbp, nbc, 3, 0, tol, false, st))) return rc;
+    if ((rc = exi_sums(w, w.X, nbp, w.Pd, nbp, w.X, nbp, w.Wz, nbp, nbc, st))) return rc;
     VG_HIP(hipMemcpyAsync(hcol.data(), w.col, sizeof(double) * 12 * 64, hipMemcpyDeviceToHost, st));
     VG_HIP(hipStreamSynchronize(st));
     for (int k = 0; k < 64; ++k) { d2[k] = hcol[512 + k]; dI[k] = hcol[576 + k]; }
-    if ((rc = exi_dots(w, y, 1, w.alpha, 1, nullptr, 0, nullptr, 0, 1, 3, 0, tol, false, st))) return rc;
+    if ((rc = exi_sums(w, y, 1, w.alpha, 1, nullptr, 0, nullptr, 0, 1, st))) return rc;
     VG_HIP(hipMemcpyAsync(hcol.data(), w.col, sizeof(double) * 12 * 64, hipMemcpyDeviceToHost, st));
     VG_HIP(hipStreamSynchronize(st));
     const double yalpha = hcol[512];
@@ -721,7 +650,7 @@ extern "C" int vggp_exact_step_iter(vggp_ctx* c, const double* y, const double t
             tz[j] = j == 0 ? 1.0 : 0.0;
         }
         double q = 0.0;
-        if (!exi_slq(td, te, tz, k, &q)) {
+        if (vg_lanczos_logquad(td.data(), te.data(), tz.data(), k, &q) != 0) {      // (lanczos_quad.h: the routine of vgi_slq_kernel)
             exi_fill_info(info, jit, n_probes, iters, -1);
             vg_set_error("vggp_exact_step_iter: the Lanczos quadrature of probe %d failed", cidx);
             return VGGP_ENOCONV;
@@ -762,7 +691,7 @@ static int exi_solve_block(VgExactIter& w, const char* fn, double tol, int max_i
         vg_set_error("%s: %d columns not converged after %d iterations (tol %g)", fn, nact, iters, tol);
         return VGGP_ENOCONV;
     }
-    return exi_dots(w, w.Bk, 64, w.X, 64, nullptr, 0, nullptr, 0, cn, 3, 0, tol, false, st);
+    return exi_sums(w, w.Bk, 64, w.X, 64, nullptr, 0, nullptr, 0, cn, st);
 }
 
 extern "C" int vggp_exact_posterior_iter(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double tol, int max_iter, double* mean,
@@ -778,7 +707,7 @@ extern "C" int vggp_exact_posterior_iter(vggp_ctx* c, const double* xs1, const d
     if (ns == 0) return VGGP_OK;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    if ((rc = exi_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     const double s = w.theta[2] * w.theta[3], inv1 = 1.0 / w.theta[0], inv2 = 1.0 / w.theta[1];
     const ExiKmv a{xs1, xs2, w.x1, w.x2, w.alpha, mean, nullptr, nullptr, (int)ns, (int)w.N, 1, 1L, 1L, inv1, inv2, s, nullptr, 0.0};
     VG_HIP(exi_kmv_launch(w.kind1, w.kind2, a, st));                   // mean = s K0(x*, X) alpha
@@ -820,7 +749,7 @@ extern "C" int vggp_exact_readout_iter(vggp_ctx* c, const double* C1, int64_t mv
     exi_fill_info(info, 0.0, 0, 0, 0);
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
-    if ((rc = exi_quiesce(c))) return rc;
+    if ((rc = vg_quiesce(c))) return rc;
     const long N = w.N;
     const double s = w.theta[2] * w.theta[3], v = w.theta[4];
     // mean = s C1 diag(alpha) C2^T: one GEMM over the points (split into slabs added in order)

@@ -12,6 +12,8 @@
 //              single-workgroup kernel (chol.hip), panels and trailing updates by the MFMA GEMM; then the blocked
 //              inverse of the factor and Sigma~^{-1} = L^{-T} L^{-1} by GEMM
 //   gradient   analytic, from Sigma~^{-1}, its partial traces, <Sigma~^{-1}, Phi~'_d> and three n2 x n1 products.
+#include "arena.h"
+#include "block_pcg.h"
 #include "ctx.h"
 #include "lanczos_quad.h"
 
@@ -219,40 +221,34 @@ struct VgMasked {
     size_t bytes = 0;
 };
 
-static void vgm_layout(VgMasked& w, char* base, size_t& off) {
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~size_t(255);
-        double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return p;
-    };
+static void vgm_layout(VgMasked& w, VgArena& a) {
     const size_t M = w.M, MM = w.iter ? 0 : M * M, n1 = w.n1, n2 = w.n2, m1 = w.m1, m2 = w.m2;
     const size_t mmax2 = m1 > m2 ? m1 * m1 : m2 * m2;
     if (!w.iter) {
-        w.Sg = take(MM); w.Lg = take(MM); w.Xg = take(MM); w.Sinv = take(MM); w.R = take(MM); w.Phip = take(2 * MM);
-        w.DI = take((size_t)w.nblk * VG_MB * VG_MB); w.Tmp = take((size_t)VG_MB * M);
-        w.PP1 = take(m1 * m1 * n1); w.PP1v = take(m1 * m1 * n1); w.PP2 = take(m2 * m2 * n2); w.PP2v = take(m2 * m2 * n2);
+        w.Sg = a.take(MM); w.Lg = a.take(MM); w.Xg = a.take(MM); w.Sinv = a.take(MM); w.R = a.take(MM); w.Phip = a.take(2 * MM);
+        w.DI = a.take((size_t)w.nblk * VG_MB * VG_MB); w.Tmp = a.take((size_t)VG_MB * M);
+        w.PP1 = a.take(m1 * m1 * n1); w.PP1v = a.take(m1 * m1 * n1); w.PP2 = a.take(m2 * m2 * n2); w.PP2v = a.take(m2 * m2 * n2);
     }
     const size_t grid = w.scattered ? n1 : n1 * n2;            // scattered: zb, zv1, zv2 are per-point vectors
     // T: the assembly's n1 x m2^2 buffer, later slab scratch of the long-K products (scattered / iterative: only the latter)
-    w.T = take((w.scattered || w.iter) ? std::max<size_t>(256 * mmax2, 64 * n1) : n1 * m2 * m2);
-    w.Tv = take((w.scattered || w.iter) ? 256 : n1 * m2 * m2);
-    w.UB = take(m1 * n2); w.UV = take(m1 * n2); w.Zb = take(grid); w.Zv1 = take(grid); w.Zv2 = take(grid);
-    w.B1s = take(m1 * n1); w.B2s = take(m2 * n2);
-    w.nb1 = take(n1); w.nb2 = take(n2); w.hv1 = take(n1); w.hv2 = take(n2); w.wn1 = take(n2);
+    w.T = a.take((w.scattered || w.iter) ? std::max<size_t>(256 * mmax2, 64 * n1) : n1 * m2 * m2);
+    w.Tv = a.take((w.scattered || w.iter) ? 256 : n1 * m2 * m2);
+    w.UB = a.take(m1 * n2); w.UV = a.take(m1 * n2); w.Zb = a.take(grid); w.Zv1 = a.take(grid); w.Zv2 = a.take(grid);
+    w.B1s = a.take(m1 * n1); w.B2s = a.take(m2 * n2);
+    w.nb1 = a.take(n1); w.nb2 = a.take(n2); w.hv1 = a.take(n1); w.hv2 = a.take(n2); w.wn1 = a.take(n2);
     const size_t wn2len = w.scattered ? 0 : n1;                 // (scattered: the all-reduce payload is C, C1, C2 | R3, the same
     // length on every rank whatever its number of points).  Iterative scattered step: its Gram matrices live in the payload too,
     // G2 in the slack and G1 behind C2 (vgi_g1_offset), so that one collective carries G2 | C0, C1, C2 | G1
     const size_t g1len = (w.iter && w.scattered) ? 32 + m1 * m1 : 0;
-    w.mpay = take(2 * m2 * m2 + 3 * M + wn2len + 3 * MM + 8 + g1len);
-    w.wn2 = base ? w.mpay + 2 * m2 * m2 + 3 * M : nullptr;
-    w.R3 = base ? w.wn2 + wn2len : nullptr;
-    w.scal = take(32);
-    w.PT1 = take(m1 * m1); w.PT2 = take(m2 * m2); w.PTS1 = take(m1 * m1); w.PTS2 = take(m2 * m2);
-    w.MkA1 = take(M); w.MkA2 = take(M); w.a0 = take(M);
-    w.partial = take(VG_MD_MAXJOBS * VG_MD_NPART); w.out = take(8);
-    w.cholscratch = take(VG_MB * (VG_MB + 1)); w.choljit = take(8);
-    w.cholstatus = reinterpret_cast<int*>(take(8));
+    w.mpay = a.take(2 * m2 * m2 + 3 * M + wn2len + 3 * MM + 8 + g1len);
+    w.wn2 = a.base ? w.mpay + 2 * m2 * m2 + 3 * M : nullptr;
+    w.R3 = a.base ? w.wn2 + wn2len : nullptr;
+    w.scal = a.take(32);
+    w.PT1 = a.take(m1 * m1); w.PT2 = a.take(m2 * m2); w.PTS1 = a.take(m1 * m1); w.PTS2 = a.take(m2 * m2);
+    w.MkA1 = a.take(M); w.MkA2 = a.take(M); w.a0 = a.take(M);
+    w.partial = a.take(VG_MD_MAXJOBS * VG_MD_NPART); w.out = a.take(8);
+    w.cholscratch = a.take(VG_MB * (VG_MB + 1)); w.choljit = a.take(8);
+    w.cholstatus = reinterpret_cast<int*>(a.take(8));
 }
 
 // iterative scattered step: G1 sits behind [G2 | . | C0, C1, C2] in w.mpay, on a 256-byte boundary
@@ -271,12 +267,11 @@ static int vgm_prepare(vggp_ctx* c, bool iter = false) {
     w->ib_valid = false;
     w->M = m1 * m2; w->m1 = (int)m1; w->m2 = (int)m2; w->n1 = c->desc.n1; w->n2 = c->desc.n2; w->scattered = sc; w->iter = iter;
     w->nblk = (int)((w->M + VG_MB - 1) / VG_MB);
-    size_t off = 0;
-    vgm_layout(*w, nullptr, off);
-    w->bytes = off + 4096;
+    const auto lay = [&](VgArena& a) { vgm_layout(*w, a); };
+    w->bytes = vg_arena_measure(lay);
     {   // say what does not fit instead of failing inside hipMalloc (the scattered / masked assemblies are not chunked over N)
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && w->bytes > free_b) {
+        size_t free_b = 0;
+        if (!vg_arena_fits(w->bytes, &free_b)) {
             vg_set_error("the dense M-space workspace of this %s step needs %.1f GiB (M = %ld, n1 = %ld, n2 = %ld, m1 = %ld, m2 = %ld; "
                          "~10 M^2 + (m1^2 + m2^2) N doubles) but only %.1f GiB of device memory are free%s",
                          sc ? "scattered" : "masked", (double)w->bytes / 1073741824.0, (long)(m1 * m2), (long)c->desc.n1, (long)c->desc.n2,
@@ -286,11 +281,7 @@ static int vgm_prepare(vggp_ctx* c, bool iter = false) {
             return VGGP_ENOMEM;
         }
     }
-    VG_HIP(hipMalloc(&w->mem, w->bytes));
-    VG_HIP(hipMemset(w->mem, 0, w->bytes));
-    off = 0;
-    vgm_layout(*w, reinterpret_cast<char*>(w->mem), off);
-    return VGGP_OK;
+    return vg_arena_alloc(&w->mem, w->bytes, lay);
 }
 
 void vg_masked_new_plan(vggp_ctx* c) {          // vggp_plan: the iterative step's kept preconditioner basis belongs to the old plan
@@ -1068,6 +1059,7 @@ struct VgIter {
     double *T1;                                   // [n1][nbc][max(m1, m2)] (masked data only)
     double *F0, *F1, *F2;                         // fields [n1][nbc][n2]; scattered points: [nbc][N]
     double *alh, *beh;                            // [maxit][nbc] PCG coefficients
+    double *part;                                 // [2][nbc] the PCG's column dots on their way to the scalars (one chunk)
     double *col;                                  // per-column scalars: [0] rz, [1] pAp, [2] r0^2, [3] rr, [4] alpha, [5] beta, [6] active, [7] k
     double *Rr1, *Rr2, *Rv1, *Rv2, *RR1, *RRV1, *RR2, *RRV2, *TW, *TWv, *Ex;   // rotated factors and the exact traces' temporaries
     double *dg1, *dg2, *Tq;                       // diag(Q^T Mk Q), m x m temporary
@@ -1079,20 +1071,6 @@ struct VgIter {
     int* nact;                                    // device word: number of active columns
 };
 
-__device__ __forceinline__ unsigned long long vgi_mix(unsigned long long x) {       // splitmix64 finaliser
-    x += 0x9E3779B97F4A7C15ULL;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-    return x ^ (x >> 31);
-}
-// block[a][c][b] = +-1 for probe columns c >= 1 (counter-based: the same probes on every device, every run), 0 for column 0
-__global__ void vgi_probe_kernel(double* blk, int m1, int nbc, int m2, unsigned long long seed) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)m1 * nbc * m2) return;
-    const int b = (int)(idx % m2), c = (int)((idx / m2) % nbc), a = (int)(idx / ((long)m2 * nbc));
-    const unsigned long long h = vgi_mix(seed ^ vgi_mix(((unsigned long long)c << 40) ^ ((unsigned long long)a * m2 + b)));
-    blk[idx] = c == 0 ? 0.0 : ((h >> 17) & 1ULL ? 1.0 : -1.0);
-}
 // out[a][c][b] = in[a][c][b] * f(dP[a][b]),  dP = 1 + rho p max(lam1,0) max(lam2,0);  mode 0: 1/dP, 1: sqrt(dP), 2: 1/sqrt(dP)
 __global__ void vgi_scale_kernel(const double* in, double* out, const double* lam1, const double* lam2, const double* theta, double p,
                                  int m1, int nbc, int m2, int mode, int c_from) {
@@ -1151,38 +1129,6 @@ __global__ __launch_bounds__(256) void vgi_coldots_kernel(const double* A, const
         out0[c] = (red[0] + red[1]) + (red[2] + red[3]);
         if (out1) out1[c] = (red[4] + red[5]) + (red[6] + red[7]);
     }
-}
-// PCG scalar logic, one lane per column.  col: [0] rz, [1] pAp, [2] r0^2, [3] rr, [4] alpha, [5] beta, [6] active, [7] k (rows of nbc)
-__global__ void vgi_pcg_scalars_kernel(double* col, int nbc, int phase, int it, double tol, double* alh, double* beh, int* nact) {
-    const int c = threadIdx.x;
-    double *rz = col, *pAp = col + nbc, *r02 = col + 2 * nbc, *rr = col + 3 * nbc, *al = col + 4 * nbc, *be = col + 5 * nbc,
-           *act = col + 6 * nbc, *kc = col + 7 * nbc;
-    if (c < nbc) {
-        if (phase == 0) {                 // start: rz, rr hold <r, P^-1 r>, <r, r>
-            r02[c] = rr[c]; act[c] = rr[c] > 0.0 ? 1.0 : 0.0; kc[c] = 0.0;
-        } else if (phase == 1) {          // after pAp
-            const double a = (act[c] != 0.0 && pAp[c] > 0.0) ? rz[c] / pAp[c] : 0.0;
-            al[c] = a; alh[(long)it * nbc + c] = a;
-        } else {                          // after the new <r, P^-1 r> (in pAp's slot is NOT touched: rz_new arrives in be's slot)
-            const double rzn = be[c];
-            const double b = (act[c] != 0.0 && rz[c] > 0.0) ? rzn / rz[c] : 0.0;
-            be[c] = b; beh[(long)it * nbc + c] = b;
-            rz[c] = rzn;
-            if (act[c] != 0.0) kc[c] += 1.0;
-            if (!(rr[c] > tol * tol * r02[c])) act[c] = 0.0;
-        }
-    }
-    __syncthreads();
-    if (phase != 1 && threadIdx.x == 0) { int n = 0; for (int k = 0; k < nbc; ++k) n += act[k] != 0.0 ? 1 : 0; *nact = n; }
-}
-// x += alpha_c p, r -= alpha_c ap    /    p = z + beta_c p
-__global__ void vgi_update_kernel(double* X, double* R, double* Pd, const double* AP, const double* Zp, const double* col, int m1, int nbc,
-                                  int m2, int phase) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)m1 * nbc * m2) return;
-    const int c = (int)((idx / m2) % nbc);
-    if (phase == 1) { const double a = col[4 * nbc + c]; X[idx] += a * Pd[idx]; R[idx] -= a * AP[idx]; }
-    else Pd[idx] = Zp[idx] + col[5 * nbc + c] * Pd[idx];
 }
 // out = a + rho b   (AP = P + rho Phi~ P)
 __global__ void vgi_axpy_rho_kernel(const double* a, const double* b, const double* theta, long n, double* out) {
@@ -1296,7 +1242,7 @@ __global__ void vgi_sum_kernel(const double* part, int n, double* out, int c_fro
 //                       control-variate field sums and the three exact-trace products (vgi_exact_sum is linear in Ex)
 // Invariants:
 //   1. Every host decision is taken from all-reduced or replicated data only -- the active-column count read per iteration,
-//      VGI_ESTALE / vgi_retry_stale, the cold-versus-kept choice of vgi_basis (host counters fed by iteration counts), VGGP_ENOCONV,
+//      VG_PCG_ESTALE / vgi_retry_stale, the cold-versus-kept choice of vgi_basis (host counters fed by iteration counts), VGGP_ENOCONV,
 //      the status words -- so all ranks take the same branch and issue the same number of collectives.  The eigen-decomposition
 //      runs redundantly on the all-reduced Gram matrices.
 //   2. Every host wait inside the iterative path is vg_comm_wait, which polls the communicator: a dead peer is an error, not a hang.
@@ -1320,42 +1266,6 @@ static double vgi_obs_fraction(const vggp_ctx* c, bool scattered, double n_obs) 
     const long n1 = c->desc.n1, n2 = c->desc.n2, nt = vgi_multi(c) ? c->desc.n_total : 0;
     if (scattered) return 1.0 / (double)(nt > n1 ? nt : n1);
     return nt > n1 * n2 ? n_obs / (double)nt : n_obs / ((double)n1 * (double)n2);
-}
-
-// Two-pass arena carver.  `layout` asks for its buffers with take() in a fixed order and is called twice: first to measure (take()
-// hands out null), then, once *mem holds that many bytes, to receive 256-byte-aligned slices of it.  *grew: the arena was too small and
-// has been replaced, so whatever it kept is gone.  oom: a format with two %.1f (GiB needed, GiB free) for the VGGP_ENOMEM raised when
-// the device has less free memory than the arena needs; null: no such check, a failing hipMalloc speaks for itself.
-struct VgArena {
-    char* base = nullptr;
-    size_t off = 0;
-    double* take(size_t count) {
-        off = (off + 255) & ~size_t(255);
-        double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return p;
-    }
-};
-template <class Layout>
-static int vg_arena_carve(void** mem, size_t* bytes, const char* oom, bool* grew, Layout&& layout) {
-    VgArena a;
-    layout(a);
-    const size_t need = a.off + 4096;
-    *grew = *bytes < need;
-    if (*grew) {
-        if (*mem) { VG_HIP(hipFree(*mem)); *mem = nullptr; *bytes = 0; }
-        size_t free_b = 0, total_b = 0;
-        if (oom && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b) {
-            vg_set_error(oom, (double)need / 1073741824.0, (double)free_b / 1073741824.0);
-            return VGGP_ENOMEM;
-        }
-        VG_HIP(hipMalloc(mem, need));
-        *bytes = need;
-    }
-    a.base = reinterpret_cast<char*>(*mem);
-    a.off = 0;
-    layout(a);
-    return VGGP_OK;
 }
 
 // The step's arena (w.imem) for either data kind.  Scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N],
@@ -1386,6 +1296,7 @@ static int vgi_prepare(VgMasked& w, VgIter& it, int nbc, int maxit) {
         it.fpart = a.take(1024);                  // (its own: a block vector has M nbc doubles, which may be fewer than the 1024 partials)
         it.krs = a.take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
         it.nact = reinterpret_cast<int*>(a.take(8));
+        it.part = a.take(2 * (size_t)nbc);
     });
     if (grew || w.ib_nbc != nbc || w.ib_maxit != maxit) w.ib_valid = false;      // (the layout moves: the kept basis is gone)
     w.ib_nbc = nbc; w.ib_maxit = maxit;
@@ -1450,46 +1361,36 @@ static int vgi_apply(vggp_ctx* c, const VgMasked& w, const VgIter& it, bool fiel
     return VGGP_OK;
 }
 
-#define VGI_ESTALE (-1001)      // internal: the kept preconditioner basis is too far off (the caller repeats the step with a cold solve)
-// Block PCG for Sigma~ X = R: the right-hand sides are in it.R on entry (zero columns start inactive), the solution is in it.X on
-// return; preconditioner from d.Qt, d.lam0 and p, per-column stopping rule.  history: iteration k keeps its coefficients in row k of
-// alh / beh (the quadrature reads them) instead of overwriting row 0.  stale_limit > 0: a solve that still has active columns after
-// more iterations than that gives the kept basis up (VGI_ESTALE).  One host read-back of the active count per iteration.
+// Block PCG for Sigma~ X = R (vg_block_pcg, block_pcg.h): the right-hand sides are in it.R on entry, the solution is in it.X on return.
+// The caller object: the operator is vgi_apply, the preconditioner the rotation by d.Qt with d.lam0 and p, a column dot is ONE
+// workgroup per column (vgi_coldots_kernel into the one-chunk partial buffer it.part), and the host waits with vg_comm_wait
+// (invariant 2 above) before it reads the active count.  No read-back of that count after the start: the read-outs run one solve per
+// 64 cells.  A solve that runs past stale_limit gives the kept basis up (VG_PCG_ESTALE, vgi_retry_stale).
 static int vgi_pcg(vggp_ctx* c, VgMasked& w, const VgIter& it, double p, double tol, int max_iter, bool history, bool field2, int stale_limit,
                    int* iters_out, int* nact_out, hipStream_t st) {
-    const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
-    const long nb = w.M * nbc;
-    int rc;
-    VG_HIP(hipMemsetAsync(it.X, 0, sizeof(double) * nb, st));
-    if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-    VG_HIP(hipMemcpyAsync(it.Pd, it.Zp, sizeof(double) * nb, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, m1, nbc, m2, it.col, it.col + 3 * nbc);
-    hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 0, 0, tol, it.alh, it.beh, it.nact);
-    int iters = 0, nact = nbc;
-    for (int k = 0; k < max_iter && nact > 0; ++k) {
-        const int row = history ? k : 0;
-        if ((rc = vgi_apply(c, w, it, field2, st))) return rc;
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.Pd, it.AP, (const double*)nullptr, (const double*)nullptr, m1, nbc,
-                           m2, it.col + nbc, (double*)nullptr);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 1, row, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, m1, nbc, m2, 1);
-        if ((rc = vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st))) return rc;
-        hipLaunchKernelGGL(vgi_coldots_kernel, dim3(nbc), dim3(256), 0, st, it.R, it.Zp, it.R, it.R, m1, nbc, m2, it.col + 5 * nbc,
-                           it.col + 3 * nbc);
-        hipLaunchKernelGGL(vgi_pcg_scalars_kernel, dim3(1), dim3(64), 0, st, it.col, nbc, 2, row, tol, it.alh, it.beh, it.nact);
-        VGM_LAUNCH1D(vgi_update_kernel, nb, st, it.X, it.R, it.Pd, it.AP, it.Zp, it.col, m1, nbc, m2, 2);
-        VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
-        VGI_WAIT(c, st);
-        nact = c->h_out->counters[0][0];                               // (from replicated block vectors: the same on every rank)
-        iters = k + 1;
-        if (stale_limit > 0 && nact > 0 && iters > stale_limit) {      // the kept basis has drifted too far: not worth iterating on
-            w.ib_valid = false;
-            return VGI_ESTALE;
+    struct Ops {
+        vggp_ctx* c; VgMasked& w; const VgIter& it; double p; bool field2; hipStream_t st;
+        int apply() { return vgi_apply(c, w, it, field2, st); }
+        int precond() { return vgi_rot(c, w, it, it.R, it.Zp, 0, 0, p, st); }
+        int dots(int phase) {
+            const bool pAp = phase == 1;
+            hipLaunchKernelGGL(vgi_coldots_kernel, dim3(it.nbc), dim3(256), 0, st, pAp ? it.Pd : it.R, pAp ? it.AP : it.Zp,
+                               pAp ? (const double*)nullptr : it.R, pAp ? (const double*)nullptr : it.R, w.m1, it.nbc, w.m2, it.part,
+                               pAp ? (double*)nullptr : it.part + it.nbc);
+            return VGGP_OK;
         }
-    }
-    *iters_out = iters;
-    *nact_out = nact;
-    return VGGP_OK;
+        int active(int* nact) {
+            VG_HIP(hipMemcpyAsync(&c->h_out->counters[0][0], it.nact, sizeof(int), hipMemcpyDeviceToHost, st));
+            VGI_WAIT(c, st);
+            *nact = c->h_out->counters[0][0];                          // (from replicated block vectors: the same on every rank)
+            return VGGP_OK;
+        }
+    };
+    const VgBlockPcg b{it.X, it.R, it.Pd, it.AP, it.Zp, it.part, 1, it.col, it.nbc, it.alh, it.beh, it.nact, w.m1, it.nbc, w.m2, it.nbc,
+                       /*count_at_start=*/false};
+    const int rc = vg_block_pcg(b, Ops{c, w, it, p, field2, st}, tol, max_iter, history, stale_limit, iters_out, nact_out, st);
+    if (rc == VG_PCG_ESTALE) w.ib_valid = false;                       // the kept basis has drifted too far: not worth iterating on
+    return rc;
 }
 
 // Eigenbasis of the preconditioner from the Gram matrices G1, G2 of this step, into d.Qt / d.lam0; *reused: the kept basis serves.
@@ -1542,12 +1443,12 @@ static void vgi_basis_done(VgMasked& w, int iters) {
     if (w.ib_fresh) { w.ib_valid = true; w.ib_age = 0; w.ib_ref_its = iters; }
     w.ib_last_its = iters;
 }
-// a step that gave its kept basis up (VGI_ESTALE) runs once more, now with a cold solve
+// a step that gave its kept basis up (VG_PCG_ESTALE) runs once more, now with a cold solve
 template <class Once>
 static int vgi_retry_stale(const char* fn, Once&& once) {
     int rc = once();
-    if (rc == VGI_ESTALE) rc = once();
-    if (rc == VGI_ESTALE) { vg_set_error("%s: internal (stale basis after a cold solve)", fn); rc = VGGP_ESTATE; }
+    if (rc == VG_PCG_ESTALE) rc = once();
+    if (rc == VG_PCG_ESTALE) { vg_set_error("%s: internal (stale basis after a cold solve)", fn); rc = VGGP_ESTATE; }
     return rc;
 }
 
@@ -1556,7 +1457,7 @@ static int vgi_step_solve(vggp_ctx* c, VgMasked& w, const VgIter& it, const char
                           bool reused, int* iters, hipStream_t st) {
     const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
     int rc, nact = 0;
-    VGM_LAUNCH1D(vgi_probe_kernel, w.M * nbc, st, it.X, m1, nbc, m2, 0x5647475000000001ULL);
+    VGM_LAUNCH1D(vg_pcg_probe_kernel, w.M * nbc, st, it.X, (long)m1, nbc, m2, nbc, 0x5647475000000001ULL);
     if ((rc = vgi_rot(c, w, it, it.X, it.R, 1, 1, p, st))) return rc;
     if ((rc = vgi_rot(c, w, it, it.X, it.Wz, 2, 1, p, st))) return rc;
     VGM_LAUNCH1D(vgi_col_kernel, w.M, st, it.R, C0, m1, nbc, m2, 0, 0);
@@ -1874,8 +1775,6 @@ __global__ __launch_bounds__(256) void vgi_readout_reduce_kernel(const double* T
     }
 }
 
-// the outputscale's exponent in q(v): -1 for the inter-domain bases (VFF, B1)
-static int vgi_scale_exp(const VgDim& d) { return (d.basis == VGGP_BASIS_VFF || d.basis == VGGP_BASIS_B1) ? -1 : 1; }
 // q(v) mean of every cell from the a0 an iterative step left: L0_1 A0 L0_2^T, scaled as vggp_qv_masked scales it (two GEMMs, no solve)
 static int vgi_qv_mean(vggp_ctx* c, VgMasked& w, double* mean, hipStream_t st) {
     VgDim &d1 = c->d[0], &d2 = c->d[1];
@@ -1883,7 +1782,7 @@ static int vgi_qv_mean(vggp_ctx* c, VgMasked& w, double* mean, hipStream_t st) {
     int rc;
     if ((rc = gemm1(d1.L0, m1, 1, w.a0, m2, 1, w.MkA1, m2, m1, m2, m1, st))) return rc;
     if ((rc = gemm1(w.MkA1, m2, 1, d2.L0, 1, m2, mean, m2, m1, m2, m2, st))) return rc;
-    VGM_LAUNCH1D(vgm_scale_rho_kernel, w.M, st, mean, w.M, c->theta, vgi_scale_exp(d1), vgi_scale_exp(d2));
+    VGM_LAUNCH1D(vgm_scale_rho_kernel, w.M, st, mean, w.M, c->theta, vg_uexp(d1.basis), vg_uexp(d2.basis));
     VG_HIP(hipGetLastError());
     return VGGP_OK;
 }
@@ -1962,6 +1861,7 @@ static int vgi_readout_prepare(const vggp_ctx* c, VgMasked& w, VgReadout& r, int
         r.cells = reinterpret_cast<long long*>(a.take((size_t)nbc));
         it.krs = a.take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
         it.nact = reinterpret_cast<int*>(a.take(8));
+        it.part = a.take(2 * (size_t)nbc);
     });
     if (rc) return rc;
     r.p = vgi_obs_fraction(c, sc, n_obs);
@@ -2016,7 +1916,7 @@ static int vgi_readout_run(vggp_ctx* c, const char* fn, int mode, bool scattered
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
     VgDim &d1 = c->d[0], &d2 = c->d[1];
-    const int e1 = vgi_scale_exp(d1), e2 = vgi_scale_exp(d2);
+    const int e1 = vg_uexp(d1.basis), e2 = vg_uexp(d2.basis);
     if (mode == 1 && mean && (rc = vgi_qv_mean(c, w, mean, st))) return rc;
     if (ncols == 0) { VGI_WAIT(c, st); return VGGP_OK; }
     const int nbc = (int)std::min<int64_t>(block, ncols);

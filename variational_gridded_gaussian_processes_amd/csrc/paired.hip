@@ -16,6 +16,7 @@
 //               variances diag(F Q F^T) go through the same kernel with F generated from (z, x*) or from C1, C2.
 // Split reductions are summed in a fixed order (no float atomics): every result is bitwise repeatable.
 // Specification: tests/general_z_spec.py.
+#include "arena.h"
 #include "gen_gemm.h"
 
 #include <algorithm>
@@ -255,35 +256,29 @@ struct VgPaired {
     double theta[5] = {0, 0, 0, 0, 0}, eps = 0.0;
 };
 
-static void pz_layout(VgPaired& w, char* base, size_t& off) {
-    auto take = [&](size_t count) {
-        off = (off + 255) & ~size_t(255);
-        double* p = base ? reinterpret_cast<double*>(base + off) : nullptr;
-        off += count * sizeof(double);
-        return p;
-    };
+static void pz_layout(VgPaired& w, VgArena& a) {
     const size_t M = w.M, MM = M * M, n1 = w.n1, n2 = w.n2;
-    w.z1 = take(M); w.z2 = take(M); w.x1 = take(n1); w.x2 = take(n2);
-    w.K0 = take(MM); w.P0 = take(MM); w.S = take(MM); w.Lk = take(MM); w.Xk = take(MM); w.Kinv = take(MM);
-    w.Ls = take(MM); w.Xs = take(MM); w.Sinv = take(MM); w.KP = take(MM); w.KPK = take(MM); w.Pb = take(MM);
+    w.z1 = a.take(M); w.z2 = a.take(M); w.x1 = a.take(n1); w.x2 = a.take(n2);
+    w.K0 = a.take(MM); w.P0 = a.take(MM); w.S = a.take(MM); w.Lk = a.take(MM); w.Xk = a.take(MM); w.Kinv = a.take(MM);
+    w.Ls = a.take(MM); w.Xs = a.take(MM); w.Sinv = a.take(MM); w.KP = a.take(MM); w.KPK = a.take(MM); w.Pb = a.take(MM);
     for (int k = 0; k < 6; ++k) { w.G[k] = nullptr; w.A[k] = nullptr; }
     w.T = w.U = w.gslab = w.slab1 = w.bpart = w.part2 = nullptr;
     if (w.scattered) {
-        w.slab1 = w.ns1 > 1 ? take((size_t)w.ns1 * MM) : nullptr;
-        w.bpart = w.ns1 > 1 ? take((size_t)w.ns1 * M) : nullptr;
-        w.part2 = take((size_t)w.runs2 * M * 4);                 // per run of column tiles: O(M), not O(M N)
+        w.slab1 = w.ns1 > 1 ? a.take((size_t)w.ns1 * MM) : nullptr;
+        w.bpart = w.ns1 > 1 ? a.take((size_t)w.ns1 * M) : nullptr;
+        w.part2 = a.take((size_t)w.runs2 * M * 4);               // per run of column tiles: O(M), not O(M N)
     } else {
-        for (int k = 0; k < 6; ++k) w.G[k] = take(MM);
-        for (int k = 0; k < 6; ++k) w.A[k] = take(M * (k < 3 ? n1 : n2));
-        w.T = take(M * n2); w.U = take(M * n1);
+        for (int k = 0; k < 6; ++k) w.G[k] = a.take(MM);
+        for (int k = 0; k < 6; ++k) w.A[k] = a.take(M * (k < 3 ? n1 : n2));
+        w.T = a.take(M * n2); w.U = a.take(M * n1);
         const int gs = std::max(w.gsplit[0], w.gsplit[1]);
-        w.gslab = gs > 1 ? take((size_t)gs * 3 * MM) : nullptr;
+        w.gslab = gs > 1 ? a.take((size_t)gs * 3 * MM) : nullptr;
     }
-    w.DI = take((size_t)w.nblk * PZ_MB * PZ_MB); w.Tmp = take((size_t)PZ_MB * M);
-    w.cholscratch = take(PZ_MB * (PZ_MB + 1)); w.jit = take(8);
-    w.status = reinterpret_cast<int*>(take(8));
-    w.b = take(M); w.alpha = take(M); w.Pa = take(M); w.wv = take(M); w.gz1 = take(M); w.gz2 = take(M);
-    w.rowA = take(M * 8); w.rowC = take(M * 12); w.rowD = take(M * 8); w.out = take(8);
+    w.DI = a.take((size_t)w.nblk * PZ_MB * PZ_MB); w.Tmp = a.take((size_t)PZ_MB * M);
+    w.cholscratch = a.take(PZ_MB * (PZ_MB + 1)); w.jit = a.take(8);
+    w.status = reinterpret_cast<int*>(a.take(8));
+    w.b = a.take(M); w.alpha = a.take(M); w.Pa = a.take(M); w.wv = a.take(M); w.gz1 = a.take(M); w.gz2 = a.take(M);
+    w.rowA = a.take(M * 8); w.rowC = a.take(M * 12); w.rowD = a.take(M * 8); w.out = a.take(8);
 }
 
 void vg_paired_free(vggp_ctx* c) {
@@ -343,25 +338,19 @@ int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc) {
         tmp.gsplit[1] = pz_gram_split(M, desc->n2);
     }
     tmp.nblk = (int)((M + PZ_MB - 1) / PZ_MB);
-    size_t off = 0;
-    pz_layout(tmp, nullptr, off);
-    const size_t bytes = off + 4096;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && bytes > free_b) {
-            vg_set_error("vggp_plan: the paired inducing points (M = %ld) need %.1f GiB of workspace, %.1f GiB are free", M,
-                         (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
-            return VGGP_ENOMEM;
-        }
+    const size_t bytes = vg_arena_measure([&](VgArena& a) { pz_layout(tmp, a); });
+    size_t free_b = 0;
+    if (!vg_arena_fits(bytes, &free_b)) {      // (asked while the old workspace is still there)
+        vg_set_error("vggp_plan: the paired inducing points (M = %ld) need %.1f GiB of workspace, %.1f GiB are free", M,
+                     (double)bytes / 1073741824.0, (double)free_b / 1073741824.0);
+        return VGGP_ENOMEM;
     }
     vg_paired_free(c);
     VgPaired* w = new VgPaired(tmp);
     w->mem = nullptr;
     c->paired = w;                       // owned by the context from here on (vg_paired_free releases it on any later failure)
-    VG_HIP(hipMalloc(&w->mem, bytes));
-    VG_HIP(hipMemset(w->mem, 0, bytes));
-    off = 0;
-    pz_layout(*w, reinterpret_cast<char*>(w->mem), off);
+    int rc;
+    if ((rc = vg_arena_alloc(&w->mem, bytes, [&](VgArena& a) { pz_layout(*w, a); }))) return rc;
     VG_HIP(hipMemcpy(w->z1, desc->grid1, sizeof(double) * M, hipMemcpyHostToDevice));
     VG_HIP(hipMemcpy(w->z2, desc->grid2, sizeof(double) * M, hipMemcpyHostToDevice));
     VG_HIP(hipMemcpy(w->x1, desc->x1, sizeof(double) * w->n1, hipMemcpyHostToDevice));
