@@ -506,7 +506,15 @@ int vggp_exact_kmv(vggp_ctx* ctx, int kind1, int kind2, double ell1, double ell2
  * K0[m][m], dK0/d ell [m][m] (any output pointer may be NULL).  x DEVICE [n];
  * grid DEVICE ([m+1] mesh for B0, [m] coords for POINTS).
  * Replaces _Kuu_along_dim/_Kuf_along_dim (kronecker_structure.py:702-790) and the
- * pairwise kernel_d(Z), kernel(Z, x) evaluations (:318-319, :336-337). */
+ * pairwise kernel_d(Z), kernel(Z, x) evaluations (:318-319, :336-337).
+ * Range: every ell > 0 gives finite outputs.  The B0 Kuu is evaluated as ell^2 e^{-(k-1)t} expm1(-t)^2 with
+ * t = delta / ell (delta = grid[1] - grid[0]), which neither overflows nor cancels for any t > 0 (for t -> inf the
+ * neighbour-cell covariance tends to ell^2, cells further apart underflow to 0).  At LARGE ell / delta the B0 closed forms
+ * cancel: relative error about eps * ell/delta in A0 and K0 and eps * (ell/delta)^2 in dA0 and dK0 (5e-11 at
+ * ell = 320 delta, 7e-7 at ell = 3.2e4 delta; table in DESIGN.md section 5a); with VGGP_FLAG_B0_F32_KDELTA the
+ * reference-literal three-exponential Kuu loses a further factor ell/delta.
+ * VGGP_EINVAL: ell <= 0, B0 / VFF / B1 with a kind other than Matern-1/2, a NULL grid, a NULL x with A0 or dA0 requested.
+ * n = 0 is allowed (only K0 / dK0 are written). */
 int vggp_factor_build(vggp_ctx* ctx, int kind, int basis, const double* x, int64_t n,
                       const double* grid, int64_t m, double ell, int flags,
                       double* A0, double* dA0, double* K0, double* dK0, void* stream);

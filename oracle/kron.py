@@ -58,16 +58,19 @@ def points_factor(kind, z, x, ell):
 
 
 def b0_K(m: int, delta: float, ell: float):
-    """Unit-outputscale Kuu_d and d/dell (kronecker_structure.py:723-739), stable form:
-    r_k = exp(-k t) * 4 sinh^2(t/2), r_0 = 2 (expm1(-t) + t), t = delta/ell."""
+    """Unit-outputscale Kuu_d and d/dell (kronecker_structure.py:723-739), stable form: with t = delta/ell,
+    em1 = expm1(-t), E_k = exp(-(k-1) t):  r_k = E_k em1^2, r_0 = 2 (em1 + t).  No factor grows with t, so every
+    t > 0 is finite (exp(-k t) * 4 sinh^2(t/2) overflowed for t > 710)."""
     t = delta / ell
     k = np.arange(m, dtype=np.float64)
-    r = np.exp(-k * t) * (4.0 * math.sinh(0.5 * t) ** 2)
-    r[0] = 2.0 * (math.expm1(-t) + t)
+    em1 = math.expm1(-t)
+    E = np.exp(-np.maximum(k - 1.0, 0.0) * t)
+    r = E * (em1 * em1)
+    r[0] = 2.0 * (em1 + t)
     # dr_k/dell = (delta/ell^2) [(k-1)e^{-(k-1)t} + (k+1)e^{-(k+1)t} - 2k e^{-kt}]
-    #           = (t/ell) e^{-kt} [k*4sinh^2(t/2) - 2 sinh(t)]
-    dr = (t / ell) * np.exp(-k * t) * (k * 4.0 * math.sinh(0.5 * t) ** 2 - 2.0 * math.sinh(t))
-    dr[0] = (2.0 * t / ell) * math.expm1(-t)
+    #           = (t/ell) E_k [k em1^2 + expm1(-2t)]
+    dr = (t / ell) * E * (k * (em1 * em1) + math.expm1(-2.0 * t))
+    dr[0] = (2.0 * t / ell) * em1
     idx = np.abs(np.arange(m)[:, None] - np.arange(m)[None, :])
     T, dT = r[idx], dr[idx]
     return ell * ell * T, 2.0 * ell * T + ell * ell * dT
@@ -78,7 +81,7 @@ def b0_K_f32(m: int, delta: float, ell: float):
     float64 division (kronecker_structure.py:731-733 under torch's type promotion); three-term form."""
     df = np.float32(delta)
     k = np.arange(m)
-    a0 = ((k - 1).astype(np.float32) * df).astype(np.float64)
+    a0 = (np.maximum(k - 1, 0).astype(np.float32) * df).astype(np.float64)     # (k = 0 has its own form below)
     a1 = ((k + 1).astype(np.float32) * df).astype(np.float64)
     a2 = (k.astype(np.float32) * df).astype(np.float64)
     e0, e1, e2 = np.exp(-a0 / ell), np.exp(-a1 / ell), np.exp(-a2 / ell)

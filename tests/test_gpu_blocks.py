@@ -184,6 +184,15 @@ def test_sumsq(engine):
     assert abs(engine.sumsq(y) - float((y * y).sum())) < 1e-9 * float((y * y).sum())
 
 
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 100003])
+def test_sumsq_exact_on_integers(engine, n):
+    """Integer values in [-8, 8]: every partial sum is an integer below 2^53, so any reduction order gives the exact sum --
+    lengths around the wave (64) and workgroup (256) sizes and one ragged long one, compared by equality."""
+    g = torch.Generator(device="cpu").manual_seed(n)
+    y = torch.randint(-8, 9, (n,), generator=g)
+    assert engine.sumsq(y.double().to(DEV)) == float((y * y).sum())
+
+
 @pytest.mark.parametrize("block", [False, True], ids=["scalar", "block"])
 @pytest.mark.parametrize("m", [128, 130, 150])
 def test_eigh_bitwise_repeatable(engine, m, block):

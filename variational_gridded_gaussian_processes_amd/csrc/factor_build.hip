@@ -127,11 +127,11 @@ __global__ __launch_bounds__(256) void vg_factor_kernel(const VgFactorArgs2 args
     }
     if (J.basis == VGGP_BASIS_B0 && kpart && !(J.flags & VGGP_FLAG_B0_F32_KDELTA)) {
         // Toeplitz in kd = |k - p| (vg_b0_K): everything but e^{-kd t} is a constant of the launch -- one exponential per element
-        const double t = (J.grid[1] - J.grid[0]) / ell, sh = sinh(0.5 * t), s4 = 4.0 * sh * sh, sh2 = 2.0 * sinh(t);
-        const double em1 = expm1(-t), l2 = ell * ell, toe = t / ell;
+        const double t = (J.grid[1] - J.grid[0]) / ell, em1 = expm1(-t), q = em1 * em1, em2 = expm1(-2.0 * t);
+        const double l2 = ell * ell, toe = t / ell;
         const double v_diag = l2 * 2.0 * (em1 + t), d_diag = 2.0 * ell * 2.0 * (em1 + t) + l2 * (2.0 * toe) * em1;
         auto el = [&](int kd, double& v, double& dv) {
-            const double e = exp(-(double)kd * t), r = e * s4, dr = toe * e * ((double)kd * s4 - sh2);
+            const double e = exp(-(double)(kd ? kd - 1 : 0) * t), r = e * q, dr = toe * e * ((double)kd * q + em2);
             v = kd ? l2 * r : v_diag;
             dv = kd ? 2.0 * ell * r + l2 * dr : d_diag;
         };

@@ -76,20 +76,22 @@ __device__ __forceinline__ void vg_b0_A(double a, double b, double x, double ell
 }
 
 // B0 cell-cell covariance, Toeplitz in kd = |i-j| (kronecker_structure.py:723-739), written in the
-// cancellation-free form r_k = e^{-k t} 4 sinh^2(t/2), r_0 = 2 (expm1(-t) + t), t = delta/ell.
+// cancellation-free and overflow-free form, t = delta/ell, em1 = expm1(-t), E = e^{-(k-1) t}:
+//   r_k = E em1^2                                  (= e^{-(k-1)t} + e^{-(k+1)t} - 2 e^{-kt}),   r_0 = 2 (em1 + t)
+//   dr_k/d ell = (t/ell) E (k em1^2 + expm1(-2t))  (= (delta/ell^2) [(k-1)e^{-(k-1)t} + (k+1)e^{-(k+1)t} - 2k e^{-kt}])
+// No factor grows with t (the earlier e^{-kt} 4 sinh^2(t/2) overflowed to inf * 0 for t > 710): finite for every t > 0.
 __device__ __forceinline__ void vg_b0_K(int kd, double delta, double ell, double& v, double& dv) {
     const double t = delta / ell;
+    const double em1 = expm1(-t);
     double r, dr;
     if (kd == 0) {
-        const double em1 = expm1(-t);
         r = 2.0 * (em1 + t);
         dr = (2.0 * t / ell) * em1;
     } else {
-        const double sh = sinh(0.5 * t);
-        const double s4 = 4.0 * sh * sh;
-        const double e = exp(-(double)kd * t);
-        r = e * s4;
-        dr = (t / ell) * e * ((double)kd * s4 - 2.0 * sinh(t));
+        const double q = em1 * em1;
+        const double e = exp(-(double)(kd - 1) * t);
+        r = e * q;
+        dr = (t / ell) * e * ((double)kd * q + expm1(-2.0 * t));
     }
     v = ell * ell * r;
     dv = 2.0 * ell * r + ell * ell * dr;
