@@ -522,12 +522,26 @@ int vggp_factor_build(vggp_ctx* ctx, int kind, int basis, const double* x, int64
 /* Cholesky K + jitter*I = L L^T with the psd_safe_cholesky jitter schedule (0, 1e-8,
  * 1e-7, 1e-6) and the explicit inverse of L.  K, L, Linv DEVICE [m][m] row-major.
  * Replaces the Cholesky hidden inside lazify(Kuu).inv_matmul (kronecker_structure.py:269).
- * jitter_out HOST (may be NULL). */
+ * jitter_out HOST (may be NULL).
+ * Only the LOWER triangle of K is read (i >= j), as numpy / LAPACK do: anything above the diagonal, NaN included, changes no bit
+ * of the result.  L and Linv are written as whole m x m matrices, exact zeros above the diagonal; nothing outside them is written.
+ * The lowest level that succeeds is the one returned, and it is the oracle's (oracle/kron.py chol_jitter).
+ *   m <= 128   one launch, the four levels race in four workgroups;  m > 128   blocked (128-wide panels), one attempt per level.
+ * VGGP_ENOTPD (no level is positive definite; also a K with NaN on or below the diagonal): *jitter_out = -1.0;
+ *   m <= 128: L and Linv are NaN throughout;  m > 128: L and Linv are unspecified (partly NaN).  The next call is unaffected.
+ * VGGP_EINVAL: a NULL ctx, K, L or Linv, m < 1, m > 8192 -- checked before any memory is touched (*jitter_out keeps its value). */
 int vggp_cholesky_inverse(vggp_ctx* ctx, const double* K, int64_t m, double* L, double* Linv,
                           double* jitter_out, void* stream);
 
 /* Symmetric eigendecomposition G = Q diag(lam) Q^T by parallel cyclic Jacobi.
- * G DEVICE [m][m]; lam DEVICE [m]; Qt DEVICE [m][m] with ROW j = eigenvector j. */
+ * G DEVICE [m][m]; lam DEVICE [m]; Qt DEVICE [m][m] with ROW j = eigenvector j.
+ * Any finite symmetric G is accepted: indefinite, exactly rank deficient, repeated eigenvalues (within a cluster Qt is AN orthonormal
+ * basis, not a particular one), already diagonal (lam is then the diagonal bit for bit and Qt has entries 0 and +-1 only), any overall
+ * scale whose squares stay finite (2^-200 .. 2^200 tested), and the zero matrix (lam = 0, Qt orthonormal, *sweeps_out may be 0).
+ * Order of lam: flags = 0 (scalar cyclic Jacobi) returns the pairs sorted, lam[0] >= lam[1] >= ...; VGGP_FLAG_BLOCK_JACOBI (m <= 128;
+ * larger m runs the scalar solver) returns them in no particular order.  sweeps_out HOST (may be NULL).  Bitwise repeatable.
+ * VGGP_EINVAL: a NULL ctx, G, lam or Qt, m < 1, m > 256 -- before any memory is touched;  VGGP_ENOCONV: sweep limit (60 / 30) reached.
+ * NaN or inf in G is outside the contract (the pipeline's Cholesky fails first). */
 int vggp_eigh(vggp_ctx* ctx, const double* G, int64_t m, double* lam, double* Qt,
               int32_t* sweeps_out, int flags, void* stream);
 
@@ -540,7 +554,11 @@ int vggp_gemm(vggp_ctx* ctx, const double* A, int64_t sa_m, int64_t sa_k,
 /* Triangular solve by substitution on the matrix cores: L X = R (trans = 0) or L^T X = R (trans = 1), L DEVICE [m][m]
  * lower-triangular (row-major, the upper part is not read), R, X DEVICE [m][ncols] row-major (X may alias R).
  * Blocked: 16 x 16 diagonal blocks inverted in a wave, 128 x 128 diagonal blocks solved from LDS, the rest by MFMA GEMM
- * updates (csrc/trsm.hip).  Replaces the triangular solves inside lazify(Kuu).inv_matmul (kronecker_structure.py:269). */
+ * updates (csrc/trsm.hip).  Replaces the triangular solves inside lazify(Kuu).inv_matmul (kronecker_structure.py:269).
+ * "Not read" means: no value above the diagonal of L, NaN included, reaches the result.  Componentwise backward error
+ * |op(L) X - R| <= kappa16 m u |op(L)| |X|, kappa16 = largest infinity-norm condition number of the 16 x 16 diagonal blocks (measured:
+ * below m u).  VGGP_EINVAL: a NULL ctx, L, R or X, m < 1, m > 16384, ncols < 1, m ncols >= 2^31 -- before any
+ * memory is touched. */
 int vggp_trsm(vggp_ctx* ctx, const double* L, int64_t m, const double* R, int64_t ncols, double* X, int trans, void* stream);
 
 /* Kronecker solve  X = K1^{-1} Y K2^{-T},  K_d = L_d L_d^T,  from the CHOLESKY FACTORS (BASELINE metric ii; nothing is
@@ -551,7 +569,11 @@ int vggp_trsm(vggp_ctx* ctx, const double* L, int64_t m, const double* R, int64_
  * the zero half -- a substitution sweep over n / 128 block rows is a chain of 2 n / 128 dependent launches per solve
  * (1.3 ms at n = 1024 against 0.3 ms; VGGP_KRON_SUBST=1 selects it).  L1 [n1][n1], L2 [n2][n2] lower-triangular
  * (e.g. from vggp_cholesky_inverse), Y, X DEVICE [n1][n2] (X may alias Y).
- * Replaces Kuu.inv_matmul(.) with Kuu = torch.kron(Kuu_1, Kuu_2) (kronecker_structure.py:269, :805). */
+ * Replaces Kuu.inv_matmul(.) with Kuu = torch.kron(Kuu_1, Kuu_2) (kronecker_structure.py:269, :805).
+ * Only the lower triangles of L1 and L2 are used.  The three forms (default, VGGP_KRON_SUBST=1, VGGP_KRON_FOUR=1; the switches are
+ * read once per process) compute the same X: bit for bit on exactly representable data.  The result does not depend on what earlier
+ * calls left in the context's scratch.  VGGP_EINVAL: a NULL ctx, L1, L2, Y or X, n_d < 1, n_d > 16384, n1 n2 >= 2^31 -- before any
+ * memory is touched. */
 int vggp_kron_solve(vggp_ctx* ctx, const double* L1, int64_t n1, const double* L2, int64_t n2,
                     const double* Y, double* X, void* stream);
 
