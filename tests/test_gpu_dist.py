@@ -181,7 +181,7 @@ def test_config4_four_ranks_1024x4096_slabs_vs_structured_oracle(engine):
     for _, _, mean, var in res:
         assert np.abs(mean - rm).max() <= 1e-6 * np.abs(rm).max()
         # (the posterior variance is 1e-6 of the prior variance here -- 16.8 M observations -- and still matches to 1e-6
-        # relative: the read-out after warm-started steps re-runs the eigensolve cold, api.hip vg_accurate_state)
+        # relative: the read-out after warm-started steps re-runs the eigensolve cold, step.hip vg_accurate_state)
         assert np.abs(var - rv).max() <= 1e-6 * np.abs(rv).max()
 
 
@@ -414,7 +414,7 @@ FAULT_STEP = 3          # (the step counter of a context starts at 1)
 def _fault_worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     if rank == 1:
-        os.environ["VGGP_FAULT_PARTIALS_AT"] = str(FAULT_STEP)      # this rank's partials "fail" at its 3rd step (csrc/api.hip)
+        os.environ["VGGP_FAULT_PARTIALS_AT"] = str(FAULT_STEP)      # this rank's partials "fail" at its 3rd step (csrc/step.hip)
     import torch.distributed as dist
     from oracle import dense as D
     from variational_gridded_gaussian_processes_amd import VggpError

@@ -1,9 +1,9 @@
 """The six read-outs of the full-grid step (vggp_qv, vggp_qv_cov, vggp_posterior, vggp_posterior_cov, vggp_readout, vggp_zgrad) after
 every chain of the step's state machine, against the CPU oracle.
 
-vggp_elbo_step leaves a different m-space state behind depending on the chain it ran -- a full basis, the range rows of a thin
-step, split-K slabs, a payload the context does not own -- and the read-outs reach it through three branches of csrc/api.hip
-(the thin read-out, the cold rebuild vg_accurate_state, or straight through).  Each test drives a plan along a trajectory to a
+vggp_elbo_step (csrc/step.hip) leaves a different m-space state behind depending on the chain it ran -- a full basis, the range
+rows of a thin step, split-K slabs, a payload the context does not own -- and the read-outs of csrc/api.hip reach it through three
+branches (the thin read-out, the cold rebuild vg_accurate_state of csrc/step.hip, or straight through).  Each test drives a plan along a trajectory to a
 named state, asserts through the step's diagnostics that the intended chain ran, reads everything out, and then takes three more
 steps on the same plan: a read-out that rebuilds the state replaces the basis the next step starts from.
 

@@ -98,7 +98,7 @@ int main(int argc, char** argv) {
 
     for (int phase = 0; phase < 2; ++phase) {
         if (phase == 1) {
-            // suspect: fine-grained host-coherent memory mapped into the process (as api.hip:71-74 does)
+            // suspect: fine-grained host-coherent memory mapped into the process (as vggp_create in api.hip does)
             CK(hipHostMalloc((void**)&hin, 4096, hipHostMallocDefault));
             CK(hipHostMalloc((void**)&hout, 4096, hipHostMallocDefault));
             CK(hipHostGetDevicePointer((void**)&dhin, hin, 0));

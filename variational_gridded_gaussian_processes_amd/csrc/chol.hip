@@ -643,7 +643,7 @@ __global__ __launch_bounds__(1024) void vg_chol_kernel(const VgCholArgs a) {
 }
 
 
-// ---- 128 < m <= 256: two 128-blocks, all four jitter levels side by side (api.hip vg_chol_big_enqueue) ---------------------------
+// ---- 128 < m <= 256: two 128-blocks, all four jitter levels side by side (step.hip vg_chol_big_enqueue) ---------------------------
 // Kc[lvl] = K + jitter_lvl I  (four full copies: the levels are then plain only_level0 jobs whose status words say which survived)
 __global__ void vg_jitcopy_kernel(const double* K, int m, double* Kc) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x, mm = (long)m * m;

@@ -110,7 +110,7 @@ void vg_comm_abort(vggp_ctx* c) {
 // asynchronous error state, and after VGGP_COMM_TIMEOUT_S seconds (default 120) without completion the communicator is
 // aborted and the step returns VGGP_ERCCL.  Single-rank contexts and the callback transport use the plain synchronisation.
 // seq / want: when given, completion is the arrival of the step's sequence number in the pinned result block (the last word the
-// step's last kernel writes) instead of the stream running empty -- the same test the single-rank step polls (api.hip, vg_wait_step).
+// step's last kernel writes) instead of the stream running empty -- the same test the single-rank step polls (step.hip, vg_wait_step).
 int vg_comm_wait(vggp_ctx* c, hipStream_t st, const volatile double* seq, double want) {
     if (!c->comm || !g_rccl.CommGetAsyncError) { VG_HIP(hipStreamSynchronize(st)); return VGGP_OK; }
     static const double limit_s = [] { const char* e = getenv("VGGP_COMM_TIMEOUT_S"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 120.0; }();

@@ -146,7 +146,7 @@ struct VgCholJob {
 struct VgGemmBatch;
 hipError_t vg_chol_launch(const VgCholJob* jobs, int njobs, hipStream_t st, const VgGemmBatch* rider = nullptr);   // rider: m <= 128 path only
 hipError_t vg_chol_setup();   // opt-in to large dynamic LDS
-// 128 < m <= 256 (api.hip vg_chol_big_enqueue): four jittered copies of K; selection of the lowest level that survived both blocks
+// 128 < m <= 256 (step.hip vg_chol_big_enqueue): four jittered copies of K; selection of the lowest level that survived both blocks
 hipError_t vg_jitcopy_launch(const double* K, int m, double* Kc, hipStream_t st);
 hipError_t vg_cholsel_launch(const double* Lc, const double* Dc, const int* st8, int m, double* L0, double* Dinv0, double* jitter_out,
                              int* status, hipStream_t st);
@@ -161,7 +161,7 @@ struct VgTrsmJob {
     long ldl, dinv_blk, dinv_ld;
     long r_sk, r_sc, x_sk, x_sc;
     long ncols;
-    int m;                // <= 128 (larger factors are blocked by the caller, api.hip trsm_batch)
+    int m;                // <= 128 (larger factors are blocked by the caller, api.hip vg_trsm_batch)
     int trans;            // 0: L X = R, 1: L^T X = R
     int rhs_ident = 0;    // 1: R is the m x m identity (generated in registers, R is not read): X = L^{-1} resp. L^{-T}
 };
@@ -223,7 +223,7 @@ struct VgRefineJob { const double* Gw; double* E; double* R1; int m; double tol;
                                                          // hyper-parameters, so its block of Gw is delta^2 lam_range with O(1) quotients inside,
                                                          // but only the range-null rotations matter: any basis of the null space serves)
 };
-// Newton chain (api.hip finish_enqueue): after the last iteration -- eigenvalues = diag(Gw), convergence check (largest
+// Newton chain (step.hip chain_newton): after the last iteration -- eigenvalues = diag(Gw), convergence check (largest
 // off-diagonal element against tol * ||Gw||_F / m), numerical rank; counters [0] = 0, [1] = iterations | rank << 8, [2] = 0,
 // [3] = 0; bit 1 of *err (-> VG_ESUBMISS: the host repeats the step on the regular chain) when not converged or rejected.
 struct VgNewtonCheckJob { const double* Gw; double* lam; int* counters; int* err; const int* flag; int m; int iters; double tol; double noise;

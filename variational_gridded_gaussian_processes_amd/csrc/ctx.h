@@ -1,9 +1,10 @@
-// Context and per-dimension workspace of libvggp_hip.so (shared by api.hip and masked.hip).
+// Context and per-dimension workspace of libvggp_hip.so (shared by api.hip, step.hip and masked.hip).
 #pragma once
 #include "common.h"
 
 #define VG_MAXEV 40
 #define VG_NFORK 4
+#define VG_SP_SLABS 4             // split-K slabs of the early projection S' = [A2;dA2] Y (riding in the Cholesky launch)
 
 struct VgDim {
     int kind = 0, basis = 0, n = 0, m = 0;
@@ -14,7 +15,7 @@ struct VgDim {
     double* Dinv0 = nullptr;          // [ceil(m/16)][16][16]: inverses of the diagonal blocks of L0 (left by the Cholesky launch)
     double *X = nullptr, *Mk = nullptr, *GH = nullptr, *GHslab = nullptr, *Gw = nullptr;
     double *lam0 = nullptr, *Qt = nullptr, *QtPrev = nullptr, *QtPrev2 = nullptr, *U = nullptr;
-    double *Ep = nullptr, *Fp = nullptr, *Wp = nullptr;      // prediction of the next start basis (finish_enqueue tail)
+    double *Ep = nullptr, *Fp = nullptr, *Wp = nullptr;      // prediction of the next start basis (step.hip rotate_and_reduce)
     double *TM = nullptr, *TH = nullptr, *E = nullptr, *F = nullptr, *RQ = nullptr, *RQsq = nullptr;
     double *chol_scratch = nullptr, *gwork = nullptr, *jitter = nullptr;
     double2* rotlog = nullptr;
@@ -89,7 +90,7 @@ struct vggp_ctx {
     bool use_graph = true;
     hipGraphExec_t gexec[20] = {};
     VgGraphKey gkey[20];
-    // what the accurate (cold) recompute of the read-outs needs from the last step (api.hip vg_accurate_state)
+    // what the accurate (cold) recompute of the read-outs needs from the last step (step.hip vg_accurate_state)
     bool last_warm = false, last_slabs = false, acc_valid = false;
     const double* last_payload = nullptr;
     double last_yy = 0.0;
@@ -124,7 +125,7 @@ struct vggp_ctx {
     double* h_stage = nullptr;        // pinned staging of the callback transport
     long h_stage_count = 0;
     hipStream_t poll_stream = nullptr;   // the last step's completion was seen in the pinned result block, not through the runtime:
-    bool poll_stream_valid = false;      // this stream may still be finishing its graph (api.hip vg_quiesce)
+    bool poll_stream_valid = false;      // this stream may still be finishing its graph (step.hip vg_quiesce)
     long seq = 0;                     // step sequence number (h_theta[5] -> device theta[5] -> VgHostOut::seq)
     int warm_run = 0;                 // consecutive warm-started steps (periodic cold restart bounds orthogonality drift)
     // per-stage profiling (bench.py): event e[i] is recorded after stage i-1's launches
@@ -144,8 +145,14 @@ struct vggp_ctx {
 static inline int vg_uexp(int basis) { return (basis == VGGP_BASIS_VFF || basis == VGGP_BASIS_B1) ? -1 : 1; }
 
 int vg_ensure_misc(vggp_ctx* c, size_t bytes);
-// a step whose completion was only seen in its pinned block may still be finishing on its stream: wait for that stream (api.hip)
+// ---- the full-grid step (step.hip)
+// a step whose completion was only seen in its pinned block may still be finishing on its stream: wait for that stream
 int vg_quiesce(vggp_ctx* c);
+void vg_graphs_clear(vggp_ctx* c);                       // drop every captured step graph (re-planning)
+int vg_accurate_state(vggp_ctx* c, hipStream_t st);      // read-outs after a warm step: re-run the finish half cold on the resident G, H, C
+// the partials half.  early: 1 = thin chain, 2 = regular warm chains ([C;C1;C2] is then the first rider of the eigensolver chain)
+struct VgPartials { bool reduce = true, extrap = false, fused = false, apply_ns = false; int early = 0; };
+int vg_partials_enqueue(vggp_ctx* c, const double* Y, double* payload, hipStream_t st, const VgPartials& o = VgPartials());
 int vg_comm_init(vggp_ctx* c, int n_ranks, int rank, const void* unique_id);
 void vg_comm_destroy(vggp_ctx* c);
 int vg_allreduce(vggp_ctx* c, double* buf, long count, hipStream_t st);
@@ -156,8 +163,6 @@ int vg_comm_verify(vggp_ctx* c, const char* fn);      // the iterative entries: 
 #define VG_DENSE_MB 128
 struct VgDenseChol { double *S, *L, *X, *DI, *Tmp, *scratch, *jit; int* status; long M; double* Sinv; };
 int vg_blocked_chol_inverse(const VgDenseChol& w, hipStream_t st);
-int vg_partials_enqueue(vggp_ctx* c, const double* Y, double* payload, hipStream_t st, bool reduce = true, bool extrap = false, bool fused = false,
-                        bool apply_ns = false, int early = 0);      // early: 1 = thin chain, 2 = regular warm chains ([C;C1;C2] is then the first rider)
 void vg_masked_free(vggp_ctx* c);
 // paired inducing points (paired.hip; VGGP_FLAG_PAIRED_Z): the entries of vggp.h that apply to a paired plan forward here
 int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc);
@@ -193,7 +198,7 @@ hipError_t vg_kr_back_launch(const double* L, const double* R, const double* F, 
 size_t vg_kr_sqgram_scratch(int mv1, int mv2, long N);
 hipError_t vg_kr_sqgram_launch(const double* P1, const double* P2, int mv1, int mv2, long N, double* out, double* scratch, int accum,
                                hipStream_t st);
-// batch of triangular solves, each in place on its X (api.hip trsm_batch: element (row k, column c) at X[k * sk + c * sc])
+// batch of triangular solves, each in place on its X (api.hip: element (row k, column c) at X[k * sk + c * sc])
 #define VG_TRSM_BLK 128
 struct VgTrsmSpec {
     const double* L; long ldl;

@@ -690,7 +690,7 @@ __device__ __forceinline__ void vg_jacobi_body(const VgEigJob& J, double* W, dou
     // numerically null for the new matrix too.  After a jump of the hyper-parameters (measured: > 5 % in a lengthscale) they are
     // not -- the range has moved out of the predicted subspace -- and since those rows were never re-orthonormalised the result
     // would be silently wrong.  The complement's Rayleigh quotients tell: 1e-16 lam_max on a valid start, 3e-10 at a 6 % jump.
-    // The flag makes the host repeat the step cold (api.hip: VG_ESUBMISS).
+    // The flag makes the host repeat the step cold (step.hip: VG_ESUBMISS).
     if (J.null_from > 0 && J.null_from < m && tid == 0) {
         double dm = 0.0, nm = 0.0;
         for (int w = 0; w < (nthr >> 6); ++w) { dm = fmax(dm, red[16 + w]); nm = fmax(nm, red[32 + w]); }

@@ -106,7 +106,7 @@ hipError_t vg_dstage_launch(const VgMspace* ms, hipStream_t st) {
 }
 
 // ---- final reduction: ONE workgroup -----------------------------------------------------------------------------------
-// Everything the combination needs arrives reduced: the D-stage left the row sums, the beta launch (api.hip finish_enqueue,
+// Everything the combination needs arrives reduced: the D-stage left the row sums, the beta launch (step.hip rotate_and_reduce,
 // step 9) the column sums [r2; r2l] = [1; s1 lam1] (1/D) and -- through the GEMM reduction epilogue -- the per-tile partial sums
 // of the four dot products sum(E o beta beta^T) = sum((E^T beta) o beta) etc.  One workgroup loads ~25 words per thread in a single
 // batch, sums them and writes the 6 results plus the step's diagnostics (jitter levels, status words, Jacobi counters) straight

@@ -334,7 +334,7 @@ hipError_t vg_thin_tail_launch(const VgThinTail* tt, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------------
-// Cold range finder of the thin chain (api.hip, vg_cold_thin_prepass): r steps of diagonally PIVOTED Cholesky of the Gram matrix
+// Cold range finder of the thin chain (step.hip, vg_cold_thin_prepass): r steps of diagonally PIVOTED Cholesky of the Gram matrix
 // G (m x m, numerical rank < r): G ~ sum_i l_i l_i^T, pivot = largest residual diagonal.  The columns l_i span range(G) and are
 // GRADED -- l_i has zeros at the earlier pivots and norm^2 <= the i-th largest residual -- which is what the row-by-row
 // orthonormalisation that follows needs to keep the small range directions apart from the large ones (a random sketch Omega G

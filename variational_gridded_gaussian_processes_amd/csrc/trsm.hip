@@ -40,7 +40,7 @@ struct VgTrsmArgs {
 // LDSL: the lower triangle of L is staged once per workgroup in LDS (m <= 128: 128 x 130 doubles; row stride = 2 mod 32
 // doubles, so the 16 rows x 2 k of a 32-lane ds_read_b64 group hit 32 distinct bank pairs) and every A operand is an LDS
 // read.  All right-hand-side blocks of the strip are loaded before the first MFMA, so the substitution itself never waits
-// for HBM.  (m > 128 is blocked by the caller: api.hip trsm_batch.)
+// for HBM.  (m > 128 is blocked by the caller: api.hip vg_trsm_batch.)
 template <int NB, bool LDSL>
 __device__ __forceinline__ void vg_trsm_strip(const VgTrsmJob& J, long c0, bool active, double* sL, int dbg) {
     const int lane = threadIdx.x & 63;
