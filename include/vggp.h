@@ -96,7 +96,27 @@ extern "C" {
  *   vggp_readout_masked                   C_d is [mv_d][M]; Kvu[(a, b), i] = s C1[a][i] C2[b][i] (face-split, flat a mv2 + b)
  *   vggp_posterior_masked, vggp_posterior_cov_masked   posterior(x*) from k(x*, Z)
  * Every other step or read-out (vggp_qv, vggp_qv_cov, vggp_readout, vggp_posterior, vggp_posterior_cov, the masked steps, the
- * partials / finish pair) returns VGGP_EINVAL, and so does a paired step on an n_ranks > 1 context. */
+ * partials / finish pair) returns VGGP_EINVAL, and so does a paired step on an n_ranks > 1 context.
+ * State and arguments (a refused call changes nothing: the next valid call gives the bits it would give on a fresh context):
+ *   vggp_plan              VGGP_EINVAL for a non-finite inducing coordinate or observation coordinate x1[i] / x2[i], a bad kind or
+ *                          basis, M outside [1, 16384], and the size limits (scattered N < 2^30; grid n_d < 2^24, M n_d < 2^34): all
+ *                          checked before anything is allocated or released, so the previous plan (paired or not) and the state of its
+ *                          last step stay usable.  VGGP_ENOMEM ends the previous plan.
+ *   steps                  vggp_elbo_step on a plan with VGGP_FLAG_SCATTERED and vggp_elbo_step_scattered on one without it return
+ *                          VGGP_EINVAL.  All five theta components must be positive and finite (VGGP_EINVAL otherwise); they are
+ *                          checked before any is stored, so the read-outs of the earlier step go on working and keep its bits.  A step
+ *                          that ends in VGGP_ENOTPD or a HIP error leaves no state: read-outs return VGGP_ESTATE until the next step.
+ *   read-outs, vggp_zgrad* VGGP_ESTATE until a step has succeeded on the current plan AND the current inducing points: vggp_plan and
+ *                          a successful vggp_set_inducing end the state.  The read-outs test the state before their other arguments; vggp_zgrad*
+ *                          tests null outputs and the grid / scattered entry first, so the wrong entry returns VGGP_EINVAL with or
+ *                          without a step.
+ *   vggp_zgrad*            VGGP_EINVAL for the entry that does not match the plan (grid / scattered) and for a Y / y that is not the
+ *                          pointer the last step was given (the gradient belongs to that array).
+ *   vggp_set_inducing      VGGP_EINVAL for dim outside {0, 1}, m != M, a null or non-finite z: Z and the state of the last step stay.
+ *   vggp_posterior_masked  n_star = 0 succeeds and writes nothing; n_star < 0 or >= 2^30, null pointers: VGGP_EINVAL.
+ *   vggp_posterior_cov_masked   1 <= n_star <= 8192 (with M <= 16384 this implies M n_star <= 2^27), VGGP_EINVAL otherwise, before any
+ *                          memory is touched (there is no n_star <= M condition on a paired context).
+ *   vggp_readout_masked    mv_d >= 1, mv1 mv2 < 2^30, no null pointer: VGGP_EINVAL otherwise. */
 #define VGGP_FLAG_PAIRED_Z 8
 
 typedef struct vggp_ctx vggp_ctx;

@@ -266,6 +266,7 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
     VG_ENTER_DEVICE(c->device);
     int rc;
     if (desc->flags & VGGP_FLAG_PAIRED_Z) {        // paired inducing points: a workspace of their own (paired.hip), no per-dimension plan
+        if ((rc = vg_paired_check(desc))) return rc;          // (refused arguments: the previous plan and its state stay as they are)
         c->planned = false;
         vg_graphs_clear(c);
         VG_HIP(hipDeviceSynchronize());

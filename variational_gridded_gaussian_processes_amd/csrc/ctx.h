@@ -165,6 +165,7 @@ struct VgDenseChol { double *S, *L, *X, *DI, *Tmp, *scratch, *jit; int* status; 
 int vg_blocked_chol_inverse(const VgDenseChol& w, hipStream_t st);
 void vg_masked_free(vggp_ctx* c);
 // paired inducing points (paired.hip; VGGP_FLAG_PAIRED_Z): the entries of vggp.h that apply to a paired plan forward here
+int vg_paired_check(const vggp_desc* desc);          // argument checks of a paired plan: touches no state
 int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc);
 void vg_paired_free(vggp_ctx* c);
 int vg_paired_set_inducing(vggp_ctx* c, int dim, const double* z, int64_t m);

@@ -305,7 +305,8 @@ static int pz_gram_split(long M, long n) {
     return (int)std::max(1L, std::min(s, 16L));
 }
 
-int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc) {
+// Everything a paired plan can refuse for its arguments, before the context is touched: a refused plan leaves the previous one usable.
+int vg_paired_check(const vggp_desc* desc) {
     const long M = desc->m1;
     VG_REQUIRE(desc->m1 == desc->m2, "vggp_plan: VGGP_FLAG_PAIRED_Z needs m1 == m2 == M (one coordinate pair per inducing point)");
     VG_REQUIRE(M >= 1 && M <= PZ_MAX_M, "vggp_plan: paired inducing points: M = %ld outside [1, %d]", M, PZ_MAX_M);
@@ -314,14 +315,29 @@ int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc) {
     VG_REQUIRE(desc->kind1 >= 0 && desc->kind1 <= 3 && desc->kind2 >= 0 && desc->kind2 <= 3, "vggp_plan: bad kind");
     VG_REQUIRE(desc->x1 && desc->x2 && desc->grid1 && desc->grid2, "vggp_plan: null coordinate arrays");
     VG_REQUIRE(desc->n1 >= 1 && desc->n2 >= 1, "vggp_plan: no observations");
+    if (desc->flags & VGGP_FLAG_SCATTERED) {
+        VG_REQUIRE(desc->n1 == desc->n2, "vggp_plan: scattered points need n1 == n2 (one coordinate pair per point)");
+        VG_REQUIRE(desc->n1 < (1L << 30), "vggp_plan: too many scattered points");
+    } else {
+        VG_REQUIRE(desc->n1 < (1L << 24) && desc->n2 < (1L << 24) && M * desc->n1 < (1L << 34) && M * desc->n2 < (1L << 34),
+                   "vggp_plan: grid too large for the paired inducing points");
+    }
     for (long i = 0; i < M; ++i)
         VG_REQUIRE(std::isfinite(desc->grid1[i]) && std::isfinite(desc->grid2[i]), "vggp_plan: inducing point %ld is not finite", i);
+    for (long i = 0; i < desc->n1; ++i)
+        VG_REQUIRE(std::isfinite(desc->x1[i]), "vggp_plan: observation coordinate x1[%ld] is not finite", i);
+    for (long i = 0; i < desc->n2; ++i)
+        VG_REQUIRE(std::isfinite(desc->x2[i]), "vggp_plan: observation coordinate x2[%ld] is not finite", i);
+    return VGGP_OK;
+}
+
+// (desc has passed vg_paired_check)
+int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc) {
+    const long M = desc->m1;
     VgPaired tmp;
     tmp.M = M; tmp.n1 = desc->n1; tmp.n2 = desc->n2;
     tmp.scattered = (desc->flags & VGGP_FLAG_SCATTERED) != 0;
     if (tmp.scattered) {
-        VG_REQUIRE(desc->n1 == desc->n2, "vggp_plan: scattered points need n1 == n2 (one coordinate pair per point)");
-        VG_REQUIRE(desc->n1 < (1L << 30), "vggp_plan: too many scattered points");
         tmp.N = desc->n1;
         tmp.ns1 = pz_pass1_split(M, tmp.N);
         {   // pass 2: about 8192 workgroups, each summing a run of column tiles in order (partials <= 8192 x 256 doubles + 4 M: not O(N))
@@ -331,8 +347,6 @@ int vg_paired_plan(vggp_ctx* c, const vggp_desc* desc) {
             tmp.runs2 = (int)((tiles_n + tmp.tn_per2 - 1) / tmp.tn_per2);
         }
     } else {
-        VG_REQUIRE(desc->n1 < (1L << 24) && desc->n2 < (1L << 24) && M * desc->n1 < (1L << 34) && M * desc->n2 < (1L << 34),
-                   "vggp_plan: grid too large for the paired inducing points");
         tmp.N = desc->n1 * desc->n2;
         tmp.gsplit[0] = pz_gram_split(M, desc->n1);
         tmp.gsplit[1] = pz_gram_split(M, desc->n2);
@@ -498,10 +512,10 @@ int vg_paired_step(vggp_ctx* c, const double* Y, double yy, const double theta[5
     VG_REQUIRE(w.scattered == scattered_entry, "%s: the paired context was planned %s VGGP_FLAG_SCATTERED", fn,
                w.scattered ? "with" : "without");
     VG_REQUIRE(c->n_ranks == 1 && !c->comm && !c->cb, "%s: paired inducing points (VGGP_FLAG_PAIRED_Z) are single-rank only", fn);
-    for (int i = 0; i < 5; ++i) {
+    // (all five checked before any is stored: a refused theta leaves the state of the last step, which the read-outs scale by w.theta)
+    for (int i = 0; i < 5; ++i)
         VG_REQUIRE(theta[i] > 0.0 && std::isfinite(theta[i]), "theta[%d]=%g must be positive and finite", i, theta[i]);
-        w.theta[i] = theta[i];
-    }
+    for (int i = 0; i < 5; ++i) w.theta[i] = theta[i];
     w.have_step = false;
     int st_k = 0, st_s = 0;
     // (a jitter level is retried only when Kuu itself failed)

@@ -154,10 +154,12 @@ class Engine:
         self.planned = True
         self.plan_token += 1
 
-    def plan_paired(self, kind: str, Z, x1, x2, scattered: bool = False) -> None:
-        """Paired (general) inducing points (VGGP_FLAG_PAIRED_Z): Z (M, 2) any set of points, Kuu = s (K1 o K2).  x1, x2: the grid
-        axes of Y [n2, n1], or (scattered=True) the coordinates of the N points.  The steps, zgrad*, set_inducing, qv_masked,
-        qv_cov_masked, readout(masked=True) and posterior_masked / posterior_cov(masked=True) then mean the paired model."""
+    def plan_paired(self, kind, Z, x1, x2, scattered: bool = False) -> None:
+        """Paired (general) inducing points (VGGP_FLAG_PAIRED_Z): Z (M, 2) any set of points, Kuu = s (K1 o K2).  kind: one kernel
+        name for both dimensions, or a pair (kind1, kind2).  x1, x2: the grid axes of Y [n2, n1], or (scattered=True) the
+        coordinates of the N points.  The steps, zgrad*, set_inducing, qv_masked, qv_cov_masked, readout(masked=True) and
+        posterior_masked / posterior_cov(masked=True) then mean the paired model."""
+        kind1, kind2 = (kind, kind) if isinstance(kind, str) else kind
         Zn = np.ascontiguousarray(np.asarray(Z, dtype=np.float64).reshape(-1, 2))
         z1, z2 = np.ascontiguousarray(Zn[:, 0]), np.ascontiguousarray(Zn[:, 1])
         x1, x2 = _dvec(x1), _dvec(x2)
@@ -165,7 +167,7 @@ class Engine:
             raise ValueError("scattered plan: x1 and x2 must hold one coordinate pair per point")
         M = Zn.shape[0]
         d = Desc()
-        d.kind1 = d.kind2 = KIND[kind]
+        d.kind1, d.kind2 = KIND[kind1], KIND[kind2]
         d.basis1 = d.basis2 = BASIS["points"]
         d.n1, d.n2, d.m1, d.m2 = len(x1), len(x2), M, M
         d.n_total = len(x1) if scattered else len(x1) * len(x2)
