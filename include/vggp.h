@@ -382,6 +382,38 @@ int vggp_qv(vggp_ctx* ctx, double* mean, double* var, void* stream);
 /* Dense M x M covariance Kuu Sigma^{-1} Kuu of q(v) (DEVICE, M = m1*m2; small M only). */
 int vggp_qv_cov(vggp_ctx* ctx, double* cov, void* stream);
 
+/* Joint (correlated) samples of q(v) without any M x M matrix -- what `.sample(torch.Size([S]))` gives on the MultivariateNormal the
+ * reference's q_v() returns (kronecker_structure.py:825-849).  All read-outs share one whitened form,
+ *     Cov q(v) = s1^e1 s2^e2 (L0_1 (x) L0_2) Sigma~^-1 (L0_1 (x) L0_2)^T,  Sigma~ = I + rho Phi,  rho = s1 s2 / sigma^2,  e_d as vggp_qv_masked_iter,
+ * so sample s is  V_s = mean + sqrt(s1^e1 s2^e2) L0_1 X_s L0_2^T  with Cov(vec X_s) = Sigma~^-1, and the mean is the one vggp_qv* returns.
+ *   full grid (vggp_qv_sample, state of vggp_elbo_step / vggp_elbo_finish; the route of vggp_qv_cov: the accurate state, then the kept
+ *       Q_d, 1/D, L0_d):  X_s = Sigma~^-1/2 E_s = Q1 ((Q1^T E_s Q2) o D^-1/2) Q2^T,  D = 1 + rho lam1 lam2^T,  E_s m1 x m2 standard normals.
+ *       The SYMMETRIC root: independent of the signs, order and cluster bases of the eigenvectors.  No solve, no tolerance.
+ *   iterative masked / scattered (pathwise):  Z_s = E_s + sqrt(rho) K F_s,  X_s = Sigma~^-1 Z_s, with F_s standard normals over the n1 x n2
+ *       nodes resp. the N points and K the second half of the step's operator (K F = B1 (W^T o F) B2^T resp. sum_k F_k b1_k b2_k^T), so
+ *       that Cov(vec Z_s) = Sigma~ exactly.  ONE block PCG solve per `block` <= 64 samples: the solve of vggp_qv_masked_iter /
+ *       vggp_qv_var_scattered_iter (operator, kept preconditioner basis, per-column stopping rule, the read-outs' own workspace).
+ *       tol, max_iter, block, info, W, n_obs exactly as there: info->rounds1 = largest PCG count, info->sweeps1 = number of block solves.
+ * Noise.  eps_u DEVICE [n_samples][m1][m2] is E, eps_obs DEVICE [n_samples][n2][n1] (grid; the layout of Y and W) resp. [n_samples][N]
+ * (points) is F; on the iterative entries either both are given and used as they are (values on unobserved nodes are not read into the
+ * result), or both are NULL and the noise is generated on the device by vggp_normal_fill's generator from (seed, first):
+ *       E  stream 0, idx = s M + i1 m2 + i2;     F  stream 1, idx = s n1 n2 + j n1 + i (grid), s N + k (points);     s = first + local sample.
+ * Sample s of a seed is therefore the same numbers whatever n_samples, block, or the call that asks for it: out(first = 5, n = 1) is row 5
+ * of out(first = 0, n = 70), bit for bit on the iterative entries, to rounding (1e-12) on the full grid.  A column of zero noise returns
+ * the mean bit for bit.
+ *   out   DEVICE [n_samples][m1][m2], flat cell index of vggp_qv
+ * VGGP_ESTATE unless the last finished step on the context was the matching successful step (the rules of vggp_qv_cov, vggp_qv_masked_iter,
+ * vggp_qv_var_scattered_iter); VGGP_ENOCONV when a column does not converge; VGGP_EINVAL on paired contexts, the wrong plan kind,
+ * n_samples < 1, first < 0, a NULL out, only one of eps_u / eps_obs, block > 64, and on multi-rank contexts (the message says so: the
+ * counter-based noise is what a multi-rank version will need, it is not built).  A sampling call between two steps leaves the next
+ * step's bits unchanged. */
+int vggp_qv_sample(vggp_ctx* ctx, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u, double* out, void* stream);
+int vggp_qv_sample_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, int64_t n_samples, uint64_t seed, int64_t first,
+                               const double* eps_u, const double* eps_obs, double tol, int max_iter, int block, double* out,
+                               vggp_info* info, void* stream);
+int vggp_qv_sample_scattered_iter(vggp_ctx* ctx, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u,
+                                  const double* eps_obs, double tol, int max_iter, int block, double* out, vggp_info* info, void* stream);
+
 /* Gradient of the ELBO of the LAST vggp_elbo_step with respect to the inducing-point coordinates of the "points" basis
  * (Matern12SVGP and friends register Z as a trainable Parameter, kronecker_structure.py:303-304, and let autograd differentiate
  * through kernel(Z) :318-319 and kernel(cartesian_prod(Z), x) :336-337).  Y: the same device array the step was given.
@@ -521,6 +553,15 @@ int vggp_exact_readout_iter(vggp_ctx* ctx, const double* C1, int64_t mv1, const 
 int vggp_exact_kmv(vggp_ctx* ctx, int kind1, int kind2, double ell1, double ell2, const double* xr1, const double* xr2, int64_t Nr,
                    const double* xc1, const double* xc2, int64_t Nc, const double* V, int64_t nb, double* out0, double* out1, double* out2,
                    void* stream);
+
+/* Counter-based standard normals, the noise of the vggp_qv_sample* entries (csrc/sample.hip): out[k] = element first_idx + k of the
+ * sequence (seed, stream_id), DEVICE [n].  Philox4x32-10 with the published constants (multipliers 0xD2511F53, 0xCD9E8D57; Weyl
+ * increments 0x9E3779B9, 0xBB67AE85), key = (seed & 0xffffffff, seed >> 32), counter = (c & 0xffffffff, c >> 32, stream_id, 0),
+ * c = idx >> 1; from the output words w0..w3: a = (w0 << 21) | (w1 >> 11), u1 = (a + 0.5) 2^-53, b = (w2 << 21) | (w3 >> 11),
+ * u2 = (b + 0.5) 2^-53, r = sqrt(-2 ln u1); element idx = r cos(2 pi u2) for even idx, r sin(2 pi u2) for odd idx.  u1 > 0, so
+ * |z| <= 8.66.  An element depends on (seed, stream_id, idx) alone: any split of a range gives the same bits.  The context need not
+ * be planned.  VGGP_EINVAL: a NULL ctx, stream_id < 0, first_idx < 0, n < 0, a NULL out with n > 0; n = 0 writes nothing. */
+int vggp_normal_fill(vggp_ctx* ctx, uint64_t seed, int stream_id, int64_t first_idx, int64_t n, double* out, void* stream);
 
 /* Unit-outputscale factor build for one dimension: A0[m][n], dA0/d ell [m][n],
  * K0[m][m], dK0/d ell [m][m] (any output pointer may be NULL).  x DEVICE [n];

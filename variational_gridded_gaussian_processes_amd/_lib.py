@@ -79,6 +79,10 @@ SYMBOLS = {
     "vggp_qv_masked": (_I, [_P, _P, _P, _P]),
     "vggp_qv": (_I, [_P, _P, _P, _P]),
     "vggp_qv_cov": (_I, [_P, _P, _P]),
+    "vggp_qv_sample": (_I, [_P, _I64, C.c_uint64, _I64, _P, _P, _P]),
+    "vggp_qv_sample_masked_iter": (_I, [_P, _P, _D, _I64, C.c_uint64, _I64, _P, _P, _D, _I, _I, _P, C.POINTER(Info), _P]),
+    "vggp_qv_sample_scattered_iter": (_I, [_P, _I64, C.c_uint64, _I64, _P, _P, _D, _I, _I, _P, C.POINTER(Info), _P]),
+    "vggp_normal_fill": (_I, [_P, C.c_uint64, _I, _I64, _I64, _P, _P]),
     "vggp_zgrad": (_I, [_P, _P, _P, _P, _P]),
     "vggp_zgrad_scattered": (_I, [_P, _P, _P, _P, _P]),
     "vggp_set_inducing": (_I, [_P, C.c_int, _P, C.c_int64]),

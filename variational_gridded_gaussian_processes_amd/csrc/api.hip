@@ -555,6 +555,61 @@ extern "C" int vggp_qv_cov(vggp_ctx* c, double* cov, void* stream) {
     return VGGP_OK;
 }
 
+// Joint samples of q(v) of the last full-grid step, without the M x M covariance.  Sigma~ = I + rho Phi is diagonal in the kept
+// Kronecker eigenbasis, D = 1 + rho lam1 lam2^T, so with E_s standard normal over the cells
+//     V_s = mean + sqrt(s1^e1 s2^e2) L0_1 X_s L0_2^T,   X_s = Sigma~^-1/2 E_s = Q1 ((Q1^T E_s Q2) o D^-1/2) Q2^T
+// -- the SYMMETRIC root, which does not depend on the signs, order or cluster bases of the eigenvectors.  Up to 64 samples per pass
+// on the interleaved block layout [m1][nbc][m2] of the iterative solvers: four GEMMs (L0_d Q_d comes from build_RQ) and two
+// elementwise kernels per pass.  The route of vggp_qv_cov: vg_accurate_state, then Q_d, 1/D, L0_d; the mean is vggp_qv's.
+extern "C" int vggp_qv_sample(vggp_ctx* c, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u, double* out, void* stream) {
+    static const char* fn = "vggp_qv_sample";
+    VG_NOT_PAIRED(c, fn);
+    if (c) VG_REQUIRE(c->n_ranks == 1 && !c->comm && !c->cb, "%s: joint samples run on single-rank contexts only (this context is multi-rank)", fn);
+    if (!c || !c->have_step) { vg_set_error("%s: no finished ELBO step", fn); return VGGP_ESTATE; }
+    VG_REQUIRE(n_samples >= 1 && n_samples < (1LL << 31), "%s: n_samples = %lld must be at least 1", fn, (long long)n_samples);
+    VG_REQUIRE(first >= 0 && out, "%s: bad argument", fn);
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const long m1 = c->desc.m1, m2 = c->desc.m2, M = m1 * m2;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const int e1 = vg_uexp(d1.basis), e2 = vg_uexp(d2.basis);
+    const int nbc = (int)std::min<int64_t>(64, n_samples);
+    int rc = vg_accurate_state(c, st);
+    if (rc) return rc;
+    if ((rc = build_RQ(c, st))) return rc;
+    if ((rc = vg_ensure_misc(c, (size_t)(2 * M * nbc + M) * sizeof(double)))) return rc;
+    double* Xa = (double*)c->misc;
+    double* Xb = Xa + M * nbc;
+    double* mean = Xb + M * nbc;
+    VG_HIP(vg_qv_weights_launch(c->theta, c->beta, c->invD, c->wq, M, st, e1, e2));                  // the mean: vggp_qv's two GEMMs
+    VgGemmBatch g;
+    vg_gemm_init(&g);
+    vg_gemm_add(&g, d1.RQ, m1, 1, c->wq, m2, 1, c->T3, (int)m2, (int)m1, (int)m2, (int)m1);
+    VG_HIP(vg_gemm_launch(&g, st));
+    vg_gemm_init(&g);
+    vg_gemm_add(&g, c->T3, m2, 1, d2.RQ, 1, m2, mean, (int)m2, (int)m1, (int)m2, (int)m2);
+    VG_HIP(vg_gemm_launch(&g, st));
+    const int wide = nbc * (int)m2, tall = (int)m1 * nbc;
+    auto gemm = [&](const double* A, long sa_m, long sa_k, const double* B, long sb_k, long sb_n, double* C, int ldc, int Mr, int Nc, int K) {
+        vg_gemm_init(&g);
+        vg_gemm_add(&g, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, Mr, Nc, K);
+        return vg_gemm_launch(&g, st);
+    };
+    for (int64_t off = 0; off < n_samples; off += nbc) {
+        const int cn = (int)std::min<int64_t>(nbc, n_samples - off);
+        VG_HIP(vg_sample_block_noise_launch(Xa, eps_u ? eps_u + off * M : nullptr, seed, (unsigned long long)(first + off), (int)m1, nbc, (int)m2, cn,
+                                            st));
+        VG_HIP(gemm(d1.QtPrev, m1, 1, Xa, wide, 1, Xb, wide, (int)m1, wide, (int)m1));               // Q1^T E    (rows of QtPrev = eigenvectors)
+        VG_HIP(gemm(Xb, m2, 1, d2.QtPrev, 1, m2, Xa, (int)m2, tall, (int)m2, (int)m2));              // (.) Q2
+        VG_HIP(vg_sample_root_scale_launch(Xa, c->invD, (int)m1, nbc, (int)m2, st));                 // o D^-1/2
+        VG_HIP(gemm(Xa, m2, 1, d2.RQ, 1, m2, Xb, (int)m2, tall, (int)m2, (int)m2));                  // (.) (L0_2 Q2)^T
+        VG_HIP(gemm(d1.RQ, m1, 1, Xb, wide, 1, Xa, wide, (int)m1, wide, (int)m1));                   // (L0_1 Q1) (.)
+        VG_HIP(vg_sample_out_launch(Xa, mean, c->theta, e1, e2, (int)m1, nbc, (int)m2, cn, out + off * M, st));
+    }
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
 // posterior at scattered points, processed in chunks so the workspace stays bounded
 extern "C" int vggp_posterior(vggp_ctx* c, const double* xs1, const double* xs2, int64_t ns, double* mean, double* var,
                               void* stream) {

@@ -199,6 +199,18 @@ hipError_t vg_kr_back_launch(const double* L, const double* R, const double* F, 
 size_t vg_kr_sqgram_scratch(int mv1, int mv2, long N);
 hipError_t vg_kr_sqgram_launch(const double* P1, const double* P2, int mv1, int mv2, long N, double* out, double* scratch, int accum,
                                hipStream_t st);
+// joint samples of q(v) (sample.hip): the counter-based normal generator and the elementwise kernels around the block solves.
+// Block vectors [m1][nbc][m2], grid fields [n1][nbc][n2] (Wt [n1][n2]), point fields [nbc][N] (Wt null, n1 = N); cn live columns,
+// s0 = global number of the block's first sample; eps null: generated from (seed, s0)
+hipError_t vg_normal_fill_launch(unsigned long long seed, unsigned stream_id, unsigned long long first, long n, double* out, hipStream_t st);
+hipError_t vg_sample_block_noise_launch(double* E, const double* eps, unsigned long long seed, unsigned long long s0, int m1, int nbc, int m2,
+                                        int cn, hipStream_t st);
+hipError_t vg_sample_field_noise_launch(double* F, const double* Wt, const double* eps, unsigned long long seed, unsigned long long s0, long n1,
+                                        int nbc, long n2, int cn, hipStream_t st);
+hipError_t vg_sample_fuse_launch(double* Z, const double* K, const double* theta, long n, hipStream_t st);                 // Z += sqrt(rho) K
+hipError_t vg_sample_root_scale_launch(double* X, const double* invD, int m1, int nbc, int m2, hipStream_t st);           // X o= sqrt(invD)
+hipError_t vg_sample_out_launch(const double* Y, const double* mean, const double* theta, int e1, int e2, int m1, int nbc, int m2, int cn,
+                                double* out, hipStream_t st);                                                            // out[c] = mean + sqrt(s1^e1 s2^e2) Y[:, c, :]
 // batch of triangular solves, each in place on its X (api.hip: element (row k, column c) at X[k * sk + c * sc])
 #define VG_TRSM_BLK 128
 struct VgTrsmSpec {

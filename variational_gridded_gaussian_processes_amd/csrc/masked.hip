@@ -1724,6 +1724,7 @@ struct VgReadout {
     double *T;                  // the right-hand sides, kept for the reductions
     double *A1, *A2, *U1, *U2;  // posterior(x*): factor columns a_d(x*) and U_d = L0_d^-1 a_d  [m_d][cn]
     long long* cells;           // q(v): this block's flat cell indices
+    double* mean;               // joint samples: the q(v) mean every sample starts from  [m1][m2]
 };
 
 // T[a][c][b] = U1[a][c] U2[b][c] for the cn columns of this block (U_d: [m_d][cn]); the unused columns of a ragged block are zero
@@ -1839,8 +1840,10 @@ static int vgi_readout_defaults(vggp_ctx* c, const char* fn, bool scattered, int
 }
 
 // The read-outs' arena (w.rmem) for blocks of nbc columns, the transposed mask of a masked step in it, and the step's p.
-// post: posterior(x*) needs the factor columns.  Scattered points (n1 = N): no mask and no grid-sized buffers, fields [nbc][N]
-static int vgi_readout_prepare(const vggp_ctx* c, VgMasked& w, VgReadout& r, int nbc, bool post, const double* W, double n_obs, hipStream_t st) {
+// post: posterior(x*) needs the factor columns; sample: the joint samples need room for the mean.  Scattered points (n1 = N): no mask
+// and no grid-sized buffers, fields [nbc][N]
+static int vgi_readout_prepare(const vggp_ctx* c, VgMasked& w, VgReadout& r, int nbc, bool post, const double* W, double n_obs, hipStream_t st,
+                               bool sample = false) {
     const size_t m1 = w.m1, m2 = w.m2, n1 = w.n1, n2 = w.n2, M = w.M, mx = std::max(m1, m2);
     VgIter& it = r.it;
     const bool sc = w.scattered;
@@ -1862,6 +1865,7 @@ static int vgi_readout_prepare(const vggp_ctx* c, VgMasked& w, VgReadout& r, int
         it.krs = a.take(sc ? vg_kr_back_scratch((int)m1, (int)m2, (long)n1, nbc) : 0);
         it.nact = reinterpret_cast<int*>(a.take(8));
         it.part = a.take(2 * (size_t)nbc);
+        r.mean = a.take(sample ? M : 0);
     });
     if (rc) return rc;
     r.p = vgi_obs_fraction(c, sc, n_obs);
@@ -2156,6 +2160,72 @@ extern "C" int vggp_posterior_var_scattered_iter(vggp_ctx* c, const double* xs1,
                                                  int block, double* mean, double* var, vggp_info* info, void* stream) {
     return vgi_readout_run(c, "vggp_posterior_var_scattered_iter", 0, true, nullptr, 0.0, nullptr, xs1, xs2, ns, tol, max_iter, block, mean, var,
                            info, stream);
+}
+
+// ================================================================================================================================
+// Joint samples of q(v) after an iterative step (vggp_qv_sample_masked_iter, vggp_qv_sample_scattered_iter), pathwise and without
+// any M x M matrix.  Cov q(v) = s1^e1 s2^e2 (L0_1 (x) L0_2) Sigma~^-1 (L0_1 (x) L0_2)^T, so
+//     V_s = mean + sqrt(s1^e1 s2^e2) L0_1 X_s L0_2^T,   X_s = Sigma~^-1 Z_s,   Z_s = E_s + sqrt(rho) K F_s,
+// with E_s standard normal over the m1 x m2 cells, F_s standard normal over the data (grid nodes / points) and K the second half of
+// the step's operator (masked grid: B1 (W^T o F) B2^T; points: sum_k F_k b1_k b2_k^T): Cov(vec Z_s) = I + rho Phi~ = Sigma~ exactly
+// (W o W = W), hence Cov(vec X_s) = Sigma~^-1.  ONE block solve of the read-outs (vgi_readout_solve) serves up to 64 samples; all
+// products work on the interleaved layout [m1][nbc][m2], one GEMM each, so a sample's bits do not depend on its block.  The noise is
+// the caller's (eps_u, eps_obs) or the counter-based generator's (sample.hip).  Specification: tests/qv_sample_spec.py.
+// ================================================================================================================================
+static int vgi_sample_run(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, int64_t n_samples, uint64_t seed,
+                          int64_t first, const double* eps_u, const double* eps_obs, double tol, int max_iter, int block, double* out,
+                          vggp_info* info, void* stream) {
+    if (c && c->planned && !c->is_paired)
+        VG_REQUIRE(!vgi_multi(c), "%s: joint samples run on single-rank contexts only (this context is multi-rank)", fn);
+    int rc = vgi_readout_enter(c, fn, scattered, /*gridded=*/false, "plan the context with VGGP_FLAG_SCATTERED", "the context was planned for scattered points",
+                               "bad argument", W, n_obs, block);
+    if (rc) return rc;
+    VG_REQUIRE(n_samples >= 1 && n_samples < (1LL << 31), "%s: n_samples = %lld must be at least 1", fn, (long long)n_samples);
+    VG_REQUIRE(first >= 0 && out, "%s: bad argument", fn);
+    VG_REQUIRE((eps_u == nullptr) == (eps_obs == nullptr), "%s: eps_u and eps_obs are either both NULL (generated noise) or both given", fn);
+    if ((rc = vgi_readout_defaults(c, fn, scattered, &block, &tol, &max_iter, info))) return rc;
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const int m1 = w.m1, m2 = w.m2, e1 = vg_uexp(d1.basis), e2 = vg_uexp(d2.basis);
+    const long M = w.M, n1 = w.n1, n2 = w.n2;
+    const long nodes = scattered ? n1 : n1 * n2;
+    const int nbc = (int)std::min<int64_t>(block, n_samples);
+    VgReadout r;
+    if ((rc = vgi_readout_prepare(c, w, r, nbc, false, W, n_obs, st, /*sample=*/true))) return rc;
+    VgIter& it = r.it;
+    if ((rc = vgi_qv_mean(c, w, r.mean, st))) return rc;
+    const long nb = M * nbc;
+    int max_its = 0, solves = 0;
+    for (int64_t off = 0; off < n_samples; off += nbc) {
+        const int cn = (int)std::min<int64_t>(nbc, n_samples - off);
+        const unsigned long long s0 = (unsigned long long)(first + off);
+        VG_HIP(vg_sample_block_noise_launch(r.T, eps_u ? eps_u + off * M : nullptr, seed, s0, m1, nbc, m2, cn, st));
+        VG_HIP(vg_sample_field_noise_launch(it.F0, scattered ? nullptr : it.Wt, eps_obs ? eps_obs + off * nodes : nullptr, seed, s0, n1, nbc, n2, cn,
+                                            st));
+        if (scattered) VG_HIP(vg_kr_back_launch(d1.BV, d2.BV, it.F0, m1, m2, n1, nbc, it.AP, it.krs, st));
+        else if ((rc = vgi_back(w, it, d1.BV, it.F0, d2.BV, it.AP, st))) return rc;
+        VG_HIP(vg_sample_fuse_launch(r.T, it.AP, c->theta, nb, st));                                               // Z = E + sqrt(rho) K F
+        if ((rc = vgi_solve_block(c, w, r, fn, tol, max_iter, &solves, &max_its, info, st))) return rc;
+        if ((rc = gemm1(d1.L0, m1, 1, it.X, (long)nbc * m2, 1, it.Tm, nbc * m2, m1, nbc * m2, m1, st))) return rc;     // L0_1 X
+        if ((rc = gemm1(it.Tm, m2, 1, d2.L0, 1, m2, it.Tm2, m2, m1 * nbc, m2, m2, st))) return rc;                     // (.) L0_2^T
+        VG_HIP(vg_sample_out_launch(it.Tm2, r.mean, c->theta, e1, e2, m1, nbc, m2, cn, out + off * M, st));
+    }
+    VGI_WAIT(c, st);
+    return VGGP_OK;
+}
+extern "C" int vggp_qv_sample_masked_iter(vggp_ctx* c, const double* W, double n_obs, int64_t n_samples, uint64_t seed, int64_t first,
+                                          const double* eps_u, const double* eps_obs, double tol, int max_iter, int block, double* out,
+                                          vggp_info* info, void* stream) {
+    return vgi_sample_run(c, "vggp_qv_sample_masked_iter", false, W, n_obs, n_samples, seed, first, eps_u, eps_obs, tol, max_iter, block, out, info,
+                          stream);
+}
+extern "C" int vggp_qv_sample_scattered_iter(vggp_ctx* c, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u,
+                                             const double* eps_obs, double tol, int max_iter, int block, double* out, vggp_info* info,
+                                             void* stream) {
+    return vgi_sample_run(c, "vggp_qv_sample_scattered_iter", true, nullptr, 0.0, n_samples, seed, first, eps_u, eps_obs, tol, max_iter, block, out,
+                          info, stream);
 }
 
 // building blocks, exported for tests: the two kernels of kr.hip on caller-supplied device arrays

@@ -459,6 +459,55 @@ class Engine:
         check(self.lib.vggp_qv_cov(self._h, _ptr(cov), _stream(self.device)))
         return cov
 
+    # -- joint samples of q(v) (include/vggp.h: vggp_qv_sample*; no M x M matrix anywhere) ------------------------------
+    def normal_fill(self, seed: int, stream_id: int, first_idx: int, n: int) -> torch.Tensor:
+        """Elements first_idx .. first_idx + n of the counter-based normal sequence (seed, stream_id) (vggp_normal_fill) -> [n]."""
+        out = torch.empty(int(n), dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_normal_fill(self._h, int(seed) & (2**64 - 1), int(stream_id), int(first_idx), int(n), _ptr(out) if n else None,
+                                        _stream(self.device)))
+        return out
+
+    def _sample_noise(self, n_samples, eps_u, eps_obs, obs_shape):
+        S = int(n_samples)
+        if eps_u is not None and tuple(eps_u.shape) != (S, self.m1, self.m2):
+            raise ValueError(f"eps_u must be [n_samples={S}, m1={self.m1}, m2={self.m2}], got {tuple(eps_u.shape)}")
+        if eps_obs is not None and tuple(eps_obs.shape) != (S,) + obs_shape:
+            raise ValueError(f"eps_obs must be {(S,) + obs_shape}, got {tuple(eps_obs.shape)}")
+        return S, torch.empty(max(S, 0), self.m1, self.m2, dtype=torch.float64, device=self.device)
+
+    def qv_sample(self, n_samples: int, seed: int = 0, first: int = 0, eps_u: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """n_samples joint samples of q(v) after elbo_step (full grid) -> [n_samples, m1, m2].  eps_u [n_samples, m1, m2]: the
+        caller's standard normals; None: generated on the device, sample s = first + local of `seed` (the same numbers in any call)."""
+        S, out = self._sample_noise(n_samples, eps_u, None, ())
+        check(self.lib.vggp_qv_sample(self._h, S, int(seed) & (2**64 - 1), int(first), _ptr(eps_u), _ptr(out) if S > 0 else None,
+                                      _stream(self.device)))
+        return out
+
+    def qv_sample_masked_iter(self, W: torch.Tensor, n_obs: float, n_samples: int, seed: int = 0, first: int = 0,
+                              eps_u: Optional[torch.Tensor] = None, eps_obs: Optional[torch.Tensor] = None, tol: float = 1e-10,
+                              max_iter: int = 100, block: int = 0):
+        """Joint samples of q(v) after elbo_step_masked_iter (W, n_obs: the step's) -> ([n_samples, m1, m2], info): one block PCG
+        solve per `block` <= 64 samples.  eps_u [n_samples, m1, m2] and eps_obs [n_samples, n2, n1]: both given or both None
+        (generated from seed / first as qv_sample).  info['rounds'][0] = most PCG iterations, info['sweeps'][0] = block solves."""
+        self._check_Y(W)
+        S, out = self._sample_noise(n_samples, eps_u, eps_obs, (self.n2, self.n1))
+        info = Info()
+        check(self.lib.vggp_qv_sample_masked_iter(self._h, _ptr(W), float(n_obs), S, int(seed) & (2**64 - 1), int(first), _ptr(eps_u),
+                                                  _ptr(eps_obs), float(tol), int(max_iter), int(block), _ptr(out) if S > 0 else None,
+                                                  C.byref(info), _stream(self.device)))
+        return out, self._info(info)
+
+    def qv_sample_scattered_iter(self, n_samples: int, seed: int = 0, first: int = 0, eps_u: Optional[torch.Tensor] = None,
+                                 eps_obs: Optional[torch.Tensor] = None, tol: float = 1e-10, max_iter: int = 100, block: int = 0):
+        """Joint samples of q(v) after elbo_step_scattered_iter -> ([n_samples, m1, m2], info); eps_obs [n_samples, N]; otherwise as
+        qv_sample_masked_iter."""
+        S, out = self._sample_noise(n_samples, eps_u, eps_obs, (self.n1,))
+        info = Info()
+        check(self.lib.vggp_qv_sample_scattered_iter(self._h, S, int(seed) & (2**64 - 1), int(first), _ptr(eps_u), _ptr(eps_obs), float(tol),
+                                                     int(max_iter), int(block), _ptr(out) if S > 0 else None, C.byref(info),
+                                                     _stream(self.device)))
+        return out, self._info(info)
+
     def readout(self, C1: torch.Tensor, C2: torch.Tensor, kd1: torch.Tensor, kd2: torch.Tensor, literal: bool = True,
                 masked: bool = False):
         """Gridded read-out q(v) of B0 cell features from the inducing posterior of the last step (include/vggp.h):

@@ -101,13 +101,43 @@ class MultivariateNormal:
     """What q_v()/posterior() return: `.mean`, `.variance`, `.stddev`, `.confidence_region()` and a lazily
     materialised `.covariance_matrix` (dense, small problems only).  `variance` may be a callable: it is then evaluated once, on
     the first use of `.variance`, `.stddev` or `.confidence_region()` (the all-cell variance of the iterative masked solver costs
-    M / 64 block solves, the mean none)."""
+    M / 64 block solves, the mean none).
+    `.sample(sample_shape, seed)` draws JOINT samples where a sampler is attached: the q_v() of KroneckerStructure on full grids and on
+    both iterative solvers (engine side, no M x M matrix) and on the dense masked / scattered states up to M = 4096 (from
+    `.covariance_matrix`); this is also the q_u() of the Gridded* classes, the same distribution.  Not attached (sample raises
+    NotImplementedError): the gridded q_v() of the Gridded* classes (v != u: a joint residual Kvv - Kvu Kuu^-1 Kuv is needed),
+    posterior(x*), paired inducing points, the 1-D classes, the exact GP, multi-rank contexts."""
 
-    def __init__(self, mean: torch.Tensor, variance, cov_fn=None):
+    def __init__(self, mean: torch.Tensor, variance, cov_fn=None, sample_fn=None):
         self.mean = mean
         self._variance = variance
         self._cov_fn = cov_fn
         self._cov = None
+        self._sample_fn = sample_fn      # (n, seed, first) -> [n, *mean.shape]
+        self._next = 0                   # the next sample number of the unseeded sequence
+        self._seed0 = None
+
+    def sample(self, sample_shape=torch.Size(), seed: Optional[int] = None) -> torch.Tensor:
+        """Joint samples, sample_shape + mean.shape.  Not differentiable (there is no rsample).  With a seed the call is reproducible:
+        it returns samples 0 .. n - 1 of that seed.  Without one, successive calls on this object continue one sequence (the object
+        draws a seed once and keeps the number of the next sample)."""
+        if self._sample_fn is None:
+            raise NotImplementedError("joint samples are not available for this distribution: q_v() of the KroneckerStructure models "
+                                      "(full grid, solver='iterative', scattered_solver='iterative', dense states up to M = 4096) "
+                                      "carries a sampler; the gridded q_v() of the Gridded* classes, posterior(x*), paired inducing "
+                                      "points, the 1-D classes and the exact GP do not")
+        shape = torch.Size(sample_shape)
+        n = int(np.prod(shape)) if len(shape) else 1
+        if n < 1:
+            return torch.empty(shape + self.mean.shape, dtype=self.mean.dtype)
+        if seed is None:
+            if self._seed0 is None:
+                self._seed0 = int(torch.randint(0, 2**62, (1,)).item())
+            out = self._sample_fn(n, self._seed0, self._next)
+            self._next += n
+        else:
+            out = self._sample_fn(n, int(seed), 0)
+        return out.reshape(shape + self.mean.shape)
 
     @property
     def variance(self) -> torch.Tensor:
@@ -130,6 +160,12 @@ class MultivariateNormal:
     def confidence_region(self) -> Tuple[torch.Tensor, torch.Tensor]:
         s2 = 2.0 * self.stddev
         return self.mean - s2, self.mean + s2
+
+
+def _symmetric_root(cov: torch.Tensor) -> torch.Tensor:
+    """The symmetric square root of a covariance matrix by eigh, eigenvalues clamped at 0."""
+    w, V = torch.linalg.eigh(0.5 * (cov + cov.T))
+    return (V * w.clamp_min(0).sqrt()[None, :]) @ V.T
 
 
 class _ElboFunction(torch.autograd.Function):
@@ -389,17 +425,22 @@ class KroneckerStructure(torch.nn.Module):
 
     def q_v(self) -> MultivariateNormal:
         """gridded_kronecker_structure.py:1409-1433 == kronecker_structure.py:825-849.
-        mean is flat (M,) with u = i1*m2 + i2 (callers do `.mean.reshape(m, m).T`)."""
+        mean is flat (M,) with u = i1*m2 + i2 (callers do `.mean.reshape(m, m).T`).
+        `.sample(torch.Size([S]), seed=None)` draws joint samples [S, M]: on a full grid from the step's Kronecker eigenbasis
+        (Engine.qv_sample), on the iterative solvers by one block PCG solve per 64 samples (Engine.qv_sample_masked_iter /
+        qv_sample_scattered_iter; no solve runs before sample() is called, last_readout_info holds its PCG counts), on the dense masked /
+        scattered states from covariance_matrix up to M = 4096.  Out of scope (sample raises NotImplementedError): the gridded q_v() of
+        the Gridded* classes (v != u), posterior(x*), paired inducing points, the 1-D classes, the exact GP; multi-rank engines refuse."""
         self._refresh()
-        if self._siter and self.scattered_variances:          # the mean now, the variance of all M cells on first use (as below)
+        if self._siter and self.scattered_variances:         # the mean now, the variance of all M cells on first use (as below)
             def svar():
                 self._refresh()          # the engine may have been re-planned by another model since
                 _, v, self.last_readout_info = self._engine.qv_var_scattered_iter(tol=self.tol, max_iter=self.max_iter)
                 return v.cpu()
-            return MultivariateNormal(self._engine.qv_scattered_iter().reshape(-1).cpu(), svar)
-        if self._siter:                  # iterative scattered solver: the mean only (no solve)
+            return MultivariateNormal(self._engine.qv_scattered_iter().reshape(-1).cpu(), svar, sample_fn=self._engine_sampler())
+        if self._siter:                  # iterative scattered solver: the mean only (no solve); joint samples cost one solve per 64
             return MultivariateNormal(self._engine.qv_scattered_iter().reshape(-1).cpu(), self._scattered_iter_variance,
-                                      cov_fn=self._scattered_iter_variance)
+                                      cov_fn=self._scattered_iter_variance, sample_fn=self._engine_sampler())
         if self._iter:
             # iterative solver: the mean needs no solve and comes now; the variance of all M cells costs ceil(M / 64) block PCG
             # solves and is computed on first use (q_v_at gives it for a few cells); there is no dense covariance
@@ -408,14 +449,47 @@ class KroneckerStructure(torch.nn.Module):
             def var():
                 self._refresh()          # the engine may have been re-planned by another model since
                 return self._engine.qv_masked_iter(self._W, self._nobs, tol=self.tol, max_iter=self.max_iter)[1].cpu()
-            return MultivariateNormal(mean.reshape(-1).cpu(), var)
+            return MultivariateNormal(mean.reshape(-1).cpu(), var, sample_fn=self._engine_sampler())
         if self._masked:
             mean, var = self._engine.qv_masked()
-            return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
-                                      cov_fn=lambda: self._engine.qv_cov_masked().cpu())
+            qv = MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
+                                    cov_fn=lambda: self._engine.qv_cov_masked().cpu())
+            if not self._engine.paired:  # (paired inducing points: no sampler)
+                qv._sample_fn = self._dense_sampler(qv)
+            return qv
         mean, var = self._engine.qv()
         return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
-                                  cov_fn=lambda: self._engine.qv_cov().cpu())
+                                  cov_fn=lambda: self._engine.qv_cov().cpu(), sample_fn=self._engine_sampler())
+
+    def _engine_sampler(self):
+        """q_v().sample on a full grid and on the iterative solvers: Engine.qv_sample* (n, seed, first) -> [n, M] on the host.  No
+        solve happens before sample() is called; the iterative solvers leave their PCG counts in last_readout_info."""
+        def fn(n, seed, first):
+            self._refresh()              # the engine may have been re-planned by another model since
+            eng = self._engine
+            if self._siter:
+                out, self.last_readout_info = eng.qv_sample_scattered_iter(n, seed, first, tol=self.tol, max_iter=self.max_iter)
+            elif self._iter:
+                out, self.last_readout_info = eng.qv_sample_masked_iter(self._W, self._nobs, n, seed, first, tol=self.tol,
+                                                                        max_iter=self.max_iter)
+            else:
+                out = eng.qv_sample(n, seed, first)
+            return out.reshape(n, -1).cpu()
+        return fn
+
+    def _dense_sampler(self, qv: MultivariateNormal):
+        """q_v().sample on the dense masked / scattered states: in torch from the dense covariance (no new kernel), M <= 4096; the
+        standard normals are the engine's counter-based ones (stream 0, idx = s M + u), so a seed means the same noise everywhere."""
+        M = qv.mean.numel()
+
+        def fn(n, seed, first):
+            if M > 4096:
+                which = "scattered_solver='iterative'" if self._scattered else "solver='iterative'"
+                raise NotImplementedError(f"{type(self).__name__}: joint samples from the dense covariance stop at M = 4096 (M = {M}); "
+                                          f"build the model with {which}, whose sampler needs no M x M matrix")
+            eps = self._engine.normal_fill(seed, 0, first * M, n * M).reshape(n, M).cpu()
+            return qv.mean[None, :] + eps @ _symmetric_root(qv.covariance_matrix)
+        return fn
 
     def q_v_at(self, cells) -> MultivariateNormal:
         """q(v) at a subset of the cells (flat indices u = i1*m2 + i2): mean and variance.  On the iterative solver this costs
@@ -1022,9 +1096,10 @@ class GriddedMatern12SVGP(_GriddedReadout, KroneckerStructure):
         if self.inducing == "general":
             return qu
         idx = torch.as_tensor(self._u_of_row)
+        sample = (lambda n, seed, first: qu._sample_fn(n, seed, first)[:, idx]) if qu._sample_fn is not None else None
         if callable(qu._variance):       # iterative solvers: the variance stays lazy (block solves, or not provided: scattered)
-            return MultivariateNormal(qu.mean[idx], lambda: qu.variance[idx])
-        return MultivariateNormal(qu.mean[idx], qu.variance[idx])
+            return MultivariateNormal(qu.mean[idx], lambda: qu.variance[idx], sample_fn=sample)
+        return MultivariateNormal(qu.mean[idx], qu.variance[idx], sample_fn=sample)
 
 
 def select_inducing_mode(Z, inducing: str = "auto", rtol: float = 1e-6) -> str:
