@@ -84,11 +84,14 @@ def test_case_lists_cover_the_issue():
 
 
 def test_probe_limit_is_the_entry_s():
-    """MAX_PROBES is what masked.hip accepts (the GPU test runs that count and asserts VGGP_EINVAL one above it)."""
-    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "variational_gridded_gaussian_processes_amd", "csrc", "masked.hip")
-    with open(src) as fh:
-        limits = set(re.findall(r"VG_REQUIRE\(n_probes <= (\d+) && max_iter <= VGI_MAXIT, \"vggp_elbo_step_masked_iter", fh.read()))
+    """MAX_PROBES is what the iterative steps accept: VGI_MAX_PROBES of mspace_ws.h, which iter_step.hip checks n_probes against (the
+    GPU test runs that count and asserts VGGP_EINVAL one above it)."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "variational_gridded_gaussian_processes_amd", "csrc")
+    with open(os.path.join(csrc, "mspace_ws.h")) as fh:
+        limits = set(re.findall(r"#define VGI_MAX_PROBES (\d+)", fh.read()))
     assert limits == {str(MS.MAX_PROBES)}
+    with open(os.path.join(csrc, "iter_step.hip")) as fh:
+        assert "n_probes <= VGI_MAX_PROBES" in fh.read()
 
 
 @pytest.mark.parametrize("case", ["s96_b0_bern70_p16", "s70_pts32_track30_p1", "s96_b1_holes_p16", "s96_vff_bern05_p1"])

@@ -352,11 +352,7 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
 // the Gram matrices as little as a small move of the lengthscale does, and the subspace start checks itself (VG_ESUBMISS).  This
 // is what an optimiser that trains Z (kronecker_structure.py:303-304) calls between steps.
 extern "C" int vggp_set_inducing(vggp_ctx* c, int dim, const double* z, int64_t m) {
-    if (c && c->is_paired) {
-        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
-        VG_ENTER_DEVICE(c->device);
-        return vg_paired_set_inducing(c, dim, z, m);
-    }
+    VG_FORWARD_PAIRED(c, vg_paired_set_inducing(c, dim, z, m));
     if (!c || !c->planned) { vg_set_error("vggp_set_inducing: context not planned"); return VGGP_ESTATE; }
     VG_REQUIRE(dim == 0 || dim == 1, "vggp_set_inducing: dim must be 0 or 1");
     VgDim& d = c->d[dim];
@@ -780,11 +776,8 @@ extern "C" int vggp_readout(vggp_ctx* c, const double* C1, int64_t mv1, const do
     double* Uv = p;
     VgDim &d1 = c->d[0], &d2 = c->d[1];
     VG_HIP(vg_readout_weights_launch(c->theta, c->beta, c->invD, c->wq, m1 * m2, (flags & VGGP_READOUT_LITERAL) ? 1 : 0, st));
+    if ((rc = vg_whitened_cross(c, C1, mv1, C2, mv2, X1, X2, st))) return rc;      // X_d = Linv0_d C_d^T   (m_d x mv_d)
     VgGemmBatch g;
-    vg_gemm_init(&g);                                    // X_d = Linv0_d C_d^T            (m_d x mv_d)
-    vg_gemm_add(&g, d1.Linv0, m1, 1, C1, 1, m1, X1, (int)mv1, (int)m1, (int)mv1, (int)m1);
-    vg_gemm_add(&g, d2.Linv0, m2, 1, C2, 1, m2, X2, (int)mv2, (int)m2, (int)mv2, (int)m2);
-    VG_HIP(vg_gemm_launch(&g, st));
     vg_gemm_init(&g);                                    // T_d = Q_d^T X_d  (rows of QtPrev are the eigenvectors)
     vg_gemm_add(&g, d1.QtPrev, m1, 1, X1, mv1, 1, T1, (int)mv1, (int)m1, (int)mv1, (int)m1);
     vg_gemm_add(&g, d2.QtPrev, m2, 1, X2, mv2, 1, T2, (int)mv2, (int)m2, (int)mv2, (int)m2);
@@ -1096,11 +1089,7 @@ extern "C" int vggp_kron_solve(vggp_ctx* c, const double* L1, int64_t n1, const 
 // Uses the resident state of the last vggp_elbo_step on the same Y (warm-basis accuracy, like the lengthscale gradient); one
 // extra pass over Y (B1 Y^T), ~25 small launches.
 extern "C" int vggp_zgrad(vggp_ctx* c, const double* Y, double* gz1, double* gz2, void* stream) {
-    if (c && c->is_paired) {
-        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
-        VG_ENTER_DEVICE(c->device);
-        return vg_paired_zgrad(c, Y, gz1, gz2, stream ? (hipStream_t)stream : c->own_stream, false);
-    }
+    VG_FORWARD_PAIRED(c, vg_paired_zgrad(c, Y, gz1, gz2, stream ? (hipStream_t)stream : c->own_stream, false));
     if (!c || !c->have_step) { vg_set_error("vggp_zgrad: no finished ELBO step"); return VGGP_ESTATE; }
     VG_REQUIRE(Y && gz1 && gz2, "vggp_zgrad: null argument");
     // Row-sharded job: every term of g is a sum over observations, so each rank forms the part of ITS rows -- the columns of dimension

@@ -1,5 +1,5 @@
 // The block preconditioned conjugate-gradient solver of the library: one loop, one set of per-column scalars and one probe hash for
-// the iterative Kronecker steps with their read-outs (masked.hip) and for the iterative exact GP (exact_iter.hip).
+// the iterative Kronecker steps with their read-outs (iter_step.hip, iter_readout.hip) and for the iterative exact GP (exact_iter.hip).
 // Block vectors are [rows][nbc][inner]: [m1][nbc][m2] on the Kronecker path, [N][nbp][1] on the exact one.  What differs between the
 // two -- the operator, the preconditioner, how a column dot is summed and how the host waits -- comes in through the caller object
 // of vg_block_pcg.

@@ -188,7 +188,7 @@ int vg_allreduce(vggp_ctx* c, double* buf, long count, hipStream_t st) {
     return VGGP_OK;
 }
 
-// Does the context's collective sum over n_ranks ranks?  Asked by the iterative steps and their read-outs (masked.hip), which take host
+// Does the context's collective sum over n_ranks ranks?  Asked by the iterative steps and their read-outs (iter_step.hip, iter_readout.hip), which take host
 // decisions -- how many PCG iterations, which branch -- from all-reduced data and issue one collective per iteration: over a
 // transport that does not span the declared ranks (a callback that sums nothing, a communicator of another size) every rank would
 // count for itself and the ranks would wait for each other's collectives for ever, after computing on a fraction of the data.

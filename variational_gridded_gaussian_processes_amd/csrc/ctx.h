@@ -1,4 +1,4 @@
-// Context and per-dimension workspace of libvggp_hip.so (shared by api.hip, step.hip and masked.hip).
+// Context and per-dimension workspace of libvggp_hip.so (shared by api.hip, step.hip and the M-space solvers of mspace_ws.h).
 #pragma once
 #include "common.h"
 
@@ -64,8 +64,8 @@ struct vggp_ctx {
     long payload_len = 0;
     bool have_partials = false, have_step = false, have_masked = false;
     bool have_iter = false;          // the last finished step was a successful vggp_elbo_step_masked_iter / vggp_elbo_step_scattered_iter
-                                     // (which of the two: the plan's VGGP_FLAG_SCATTERED; their read-outs: masked.hip)
-    void* masked = nullptr;          // VgMasked workspace (masked.hip), allocated on first use
+                                     // (which of the two: the plan's VGGP_FLAG_SCATTERED; their read-outs: iter_readout.hip)
+    void* masked = nullptr;          // VgMasked workspace (mspace_ws.h), allocated on first use
     void* paired = nullptr;          // VgPaired workspace (paired.hip): allocated by a plan with VGGP_FLAG_PAIRED_Z
     bool is_paired = false;          // the current plan is a paired one: only the entries listed in vggp.h apply
     // pinned host staging
@@ -188,7 +188,21 @@ void vg_exact_iter_free(vggp_ctx* c); // iterative exact GP (exact_iter.hip)
             return VGGP_EINVAL;                                                                                         \
         }                                                                                                               \
     } while (0)
+// entries that a paired plan serves through paired.hip: `call` is the vg_paired_* forward, made on the context's device
+#define VG_FORWARD_PAIRED(c, call)                                                                                      \
+    do {                                                                                                                \
+        if ((c) && (c)->is_paired) {                                                                                    \
+            if (!(c)->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }                             \
+            VG_ENTER_DEVICE((c)->device);                                                                               \
+            return call;                                                                                                \
+        }                                                                                                               \
+    } while (0)
 void vg_masked_new_plan(vggp_ctx* c);
+// whitened read-out columns (masked_readout.hip).  columns: factor columns A_d = a_d(x*_d) of cn points and U_d = L0_d^-1 A_d
+// ([m_d][cn]);  cross: U_d = L0_d^-1 C_d^T of a gridded read-out's cross-covariances C_d [mv_d][m_d]  ([m_d][mv_d])
+int vg_whitened_columns(vggp_ctx* c, const double* xs1, const double* xs2, int cn, double* A1, double* A2, double* U1, double* U2,
+                        hipStream_t st);
+int vg_whitened_cross(vggp_ctx* c, const double* C1, long mv1, const double* C2, long mv2, double* U1, double* U2, hipStream_t st);
 // the Khatri-Rao operator of the iterative scattered step (kr.hip): L [m1][N], R [m2][N], block vectors [m1][nb][m2], fields [nb][N]
 hipError_t vg_kr_field_launch(const double* L, const double* R, const double* V, int m1, int m2, long N, int nb, double* F, hipStream_t st);
 hipError_t vg_kr_field2_launch(const double* L, const double* R, const double* V, int m1, int m2, long N, int nb, double* F, hipStream_t st);

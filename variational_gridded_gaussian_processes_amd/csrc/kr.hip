@@ -1,4 +1,4 @@
-// The Khatri-Rao operator of the iterative scattered step (masked.hip, vggp_elbo_step_scattered_iter): with one column of
+// The Khatri-Rao operator of the iterative scattered step (iter_step.hip, vggp_elbo_step_scattered_iter): with one column of
 // L (m1 x N) and R (m2 x N) per POINT and block vectors V [m1][nb][m2],
 //     field   F[c][k]      = sum_a L[a][k] sum_b V[a][c][b] R[b][k]         (the per-point scalars l_k^T V_c r_k)
 //     back    out[a][c][b] = sum_k L[a][k] F[c][k] R[b][k]
@@ -434,4 +434,58 @@ hipError_t vg_kr_sqgram_launch(const double* P1, const double* P2, int mv1, int 
     if (e != hipSuccess || direct) return e;
     hipLaunchKernelGGL(vg_kr_sqred_kernel, dim3((unsigned)((a.slab + 255) / 256)), dim3(256), 0, st, scratch, out, a.slab, ks, accum);
     return hipGetLastError();
+}
+
+// ---- building blocks, exported for tests: the kernels above on caller-supplied device arrays -------------------------------------------
+// what the three block-vector exports share: the checks, the device, the stream and the wait; launch(st) enqueues the kernel
+template <class Launch>
+static int vg_kr_export(vggp_ctx* c, const char* fn, bool non_null, int64_t m1, int64_t m2, int64_t N, int64_t nb, void* stream, Launch&& launch) {
+    if (!c) { vg_set_error("%s: null context", fn); return VGGP_EINVAL; }
+    VG_REQUIRE(non_null, "%s: null argument", fn);
+    VG_REQUIRE(m1 >= 1 && m1 <= 256 && m2 >= 1 && m2 <= 256 && nb >= 1 && nb <= 64 && N >= 1 && N < (1L << 24),
+               "%s: need 1 <= m_d <= 256, 1 <= nb <= 64, 1 <= N < 2^24", fn);
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const int rc = launch(st);
+    if (rc) return rc;
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+extern "C" int vggp_kr_field(vggp_ctx* c, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                             double* F, void* stream) {
+    return vg_kr_export(c, "vggp_kr_field", L && R && V && F, m1, m2, N, nb, stream, [&](hipStream_t st) -> int {
+        VG_HIP(vg_kr_field_launch(L, R, V, (int)m1, (int)m2, (long)N, (int)nb, F, st));
+        return VGGP_OK;
+    });
+}
+// the two-column instantiation of the field kernel (bitwise equal to vggp_kr_field; the read-outs' block solves run it)
+extern "C" int vggp_kr_field2(vggp_ctx* c, const double* L, const double* R, const double* V, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                              double* F, void* stream) {
+    return vg_kr_export(c, "vggp_kr_field2", L && R && V && F, m1, m2, N, nb, stream, [&](hipStream_t st) -> int {
+        VG_HIP(vg_kr_field2_launch(L, R, V, (int)m1, (int)m2, (long)N, (int)nb, F, st));
+        return VGGP_OK;
+    });
+}
+extern "C" int vggp_kr_back(vggp_ctx* c, const double* L, const double* R, const double* F, int64_t m1, int64_t m2, int64_t N, int64_t nb,
+                            double* out, void* stream) {
+    return vg_kr_export(c, "vggp_kr_back", L && R && F && out, m1, m2, N, nb, stream, [&](hipStream_t st) -> int {
+        const size_t sc = vg_kr_back_scratch((int)m1, (int)m2, (long)N, (int)nb);
+        const int rc = vg_ensure_misc(c, (sc + 32) * sizeof(double));
+        if (rc) return rc;
+        VG_HIP(vg_kr_back_launch(L, R, F, (int)m1, (int)m2, (long)N, (int)nb, out, (double*)c->misc, st));
+        return VGGP_OK;
+    });
+}
+extern "C" int vggp_kr_sqgram(vggp_ctx* c, const double* P1, const double* P2, int64_t mv1, int64_t mv2, int64_t N, double* out, void* stream) {
+    if (!c) { vg_set_error("vggp_kr_sqgram: null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(P1 && P2 && out, "vggp_kr_sqgram: null argument");
+    VG_REQUIRE(mv1 >= 1 && mv2 >= 1 && mv1 < (1L << 20) && mv2 < (1L << 20) && mv1 * mv2 < (1L << 28) && N >= 1 && N < (1L << 31) - 64,
+               "vggp_kr_sqgram: need mv_d >= 1, mv1 mv2 < 2^28, 1 <= N < 2^31");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    int rc = vg_ensure_misc(c, (vg_kr_sqgram_scratch((int)mv1, (int)mv2, (long)N) + 32) * sizeof(double));
+    if (rc) return rc;
+    VG_HIP(vg_kr_sqgram_launch(P1, P2, (int)mv1, (int)mv2, (long)N, out, (double*)c->misc, 0, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
 }

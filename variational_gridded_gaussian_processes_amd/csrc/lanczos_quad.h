@@ -1,5 +1,5 @@
 // Gauss quadrature of log on a Lanczos tridiagonal: the stochastic Lanczos quadrature of the iterative solvers, on the device (one
-// lane per probe: vgi_slq_kernel, masked.hip) and on the host (vggp_exact_step_iter, exact_iter.hip).
+// lane per probe: vgi_slq_kernel, iter_step.hip) and on the host (vggp_exact_step_iter, exact_iter.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>

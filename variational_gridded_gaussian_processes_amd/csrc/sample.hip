@@ -1,5 +1,5 @@
 // Joint posterior samples of q(v): the counter-based normal generator and the small kernels around the block solves
-// (vggp_normal_fill, vggp_qv_sample in api.hip, vggp_qv_sample_*_iter in masked.hip).
+// (vggp_normal_fill, vggp_qv_sample in api.hip, vggp_qv_sample_*_iter in iter_readout.hip).
 //
 // Generator: Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85),
 //     key = (seed lo, seed hi),  counter = (c lo, c hi, stream, 0),  c = idx >> 1,

@@ -257,7 +257,7 @@ int vg_partials_enqueue(vggp_ctx* c, const double* Y, double* payload, hipStream
     }
     VG_MARK(2);
 
-    if (!Y) {          // factors only (scattered step, masked.hip): B|V, X are done; Mk = X Linv0^T and nothing of the grid path
+    if (!Y) {          // factors only (scattered steps, masked.hip / iter_step.hip): B|V, X are done; Mk = X Linv0^T and nothing of the grid path
         vg_gemm_init(&g);
         for (int k = 0; k < 2; ++k) { VgDim& d = c->d[k]; vg_gemm_add(&g, d.X, d.m, 1, d.Linv0, 1, d.m, d.Mk, d.m, d.m, d.m, d.m); }
         VG_HIP(vg_gemm_launch(&g, st));
@@ -1414,11 +1414,7 @@ static int elbo_step_once(vggp_ctx* c, const double* Y, double yy_total, const d
 // since the last step; the Gram matrices depend on nothing else) skips the attempt.
 extern "C" int vggp_elbo_step(vggp_ctx* c, const double* Y, double yy_total, const double theta[5], double* elbo_out,
                               double grad_out[5], vggp_info* info, void* stream) {
-    if (c && c->is_paired) {
-        if (!c->planned) { vg_set_error("context not planned"); return VGGP_ESTATE; }
-        VG_ENTER_DEVICE(c->device);
-        return vg_paired_step(c, Y, yy_total, theta, elbo_out, grad_out, info, stream ? (hipStream_t)stream : c->own_stream, false);
-    }
+    VG_FORWARD_PAIRED(c, vg_paired_step(c, Y, yy_total, theta, elbo_out, grad_out, info, stream ? (hipStream_t)stream : c->own_stream, false));
     if (c && c->planned && theta) {
         bool jump = false;
         for (int k = 0; k < 2; ++k) jump = jump || (c->last_ell[k] > 0.0 && std::fabs(theta[k] / c->last_ell[k] - 1.0) > 0.05);
