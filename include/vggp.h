@@ -452,7 +452,10 @@ int vggp_posterior(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t 
 
 /* Dense ns x ns covariance of posterior(x*) (DEVICE [ns][ns]; ns <= 8192 and M ns <= 2^27): K** + Kuf*^T Sigma^-1 Kuf* -
  * Kuf*^T Kuu^-1 Kuf*, kronecker_structure.py:223-229, from the step's eigenbasis (never forming Sigma); the masked variant
- * from the dense Sigma~^-1 of the last masked step (ns <= M).  Callers that only need the diagonal use vggp_posterior. */
+ * from the dense Sigma~^-1 of the last masked / scattered step.  Callers that only need the diagonal use vggp_posterior.
+ * vggp_posterior_cov_masked takes 1 <= ns <= M = m1 m2 points per call (T and Sigma~^-1 T live in the step's two M x M scratch
+ * matrices and, unlike vggp_posterior_masked, a covariance cannot be chunked over the points): ns > M returns VGGP_EINVAL before
+ * anything is launched or written, and the state of the step stays readable.  (A paired context has no ns <= M condition: above.) */
 int vggp_posterior_cov(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t ns, double* cov, void* stream);
 int vggp_posterior_cov_masked(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t ns, double* cov, void* stream);
 /* Dense M x M covariance of q(v) of the last masked step (Kuu Sigma^-1 Kuu on the observed subset). */

@@ -623,7 +623,7 @@ static int masked_iter_once(vggp_ctx* c, const double* Ym, const double* W, doub
     if ((rc = gemm1(it.Wt, n2, 1, it.RR2, 1, n2, it.TW, (int)m2, (int)n1, (int)m2, (int)n2, st))) return rc;
     if ((rc = gemm1(it.Wt, n2, 1, it.RRV2, 1, n2, it.TWv, (int)m2, (int)n1, (int)m2, (int)n2, st))) return rc;
     auto exact = [&](const double* RRa, const double* TWb, double* out) -> int {
-        int r2 = gemm_longk(RRa, n1, 1, TWb, m2, 1, it.Ex, (int)m1, (int)m2, (int)n1, w.T, st);
+        int r2 = gemm_longk(RRa, n1, 1, TWb, m2, 1, it.Ex, (int)m1, (int)m2, (int)n1, w.T, w.Tcap, st);
         if (r2) return r2;
         vgi_exact_sum(c, w, it, p, out, st);
         return VGGP_OK;
@@ -705,8 +705,8 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     if ((rc = vgs_projections(c, w, y, st))) return rc;
     // Gram matrices over the points, in the payload beside the projections: G2 | . | C0, C1, C2 | G1
     double *G1 = w.mpay + vgi_g1_offset(m1, m2), *G2 = w.mpay;
-    if ((rc = gemm_longk(B1, N, 1, B1, 1, N, G1, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
-    if ((rc = gemm_longk(B2, N, 1, B2, 1, N, G2, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(B1, N, 1, B1, 1, N, G1, (int)m1, (int)m1, (int)N, w.T, w.Tcap, st))) return rc;
+    if ((rc = gemm_longk(B2, N, 1, B2, 1, N, G2, (int)m2, (int)m2, (int)N, w.T, w.Tcap, st))) return rc;
     // point-sharded job: all of them are sums over this rank's points -- the ONE collective before the solve (the gaps of the
     // payload hold zeros on every rank)
     if ((rc = vg_allreduce(c, w.mpay, (long)vgi_g1_offset(m1, m2) + m1 * m1, st))) return rc;
@@ -735,7 +735,7 @@ static int scattered_iter_once(vggp_ctx* c, const double* y, double yy, const do
     // exact parts tr(P^-1 Phi(.)) = sum (1/dP) o ((Ra o Rb)(Sa o Sb)^T): one m1 x m2 GEMM over the points each
     if ((rc = vgi_rotate_factors(c, w, it, st))) return rc;
     auto exact = [&](const double* RRa, const double* RRb, double* out) -> int {
-        int r2 = gemm_longk(RRa, N, 1, RRb, 1, N, it.Ex, (int)m1, (int)m2, (int)N, w.T, st);
+        int r2 = gemm_longk(RRa, N, 1, RRb, 1, N, it.Ex, (int)m1, (int)m2, (int)N, w.T, w.Tcap, st);
         if (r2) return r2;
         vgi_exact_sum(c, w, it, p, out, st);
         return VGGP_OK;

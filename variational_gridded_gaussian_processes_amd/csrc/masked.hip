@@ -163,8 +163,13 @@ static void vgm_layout(VgMasked& w, VgArena& a) {
         w.PP1 = a.take(m1 * m1 * n1); w.PP1v = a.take(m1 * m1 * n1); w.PP2 = a.take(m2 * m2 * n2); w.PP2v = a.take(m2 * m2 * n2);
     }
     const size_t grid = w.scattered ? n1 : n1 * n2;            // scattered: zb, zv1, zv2 are per-point vectors
-    // T: the assembly's n1 x m2^2 buffer, later slab scratch of the long-K products (scattered / iterative: only the latter)
-    w.T = a.take((w.scattered || w.iter) ? std::max<size_t>(256 * mmax2, 64 * n1) : n1 * m2 * m2);
+    // T: the assembly's n1 x m2^2 buffer, the slab scratch of vgm_colstats (min(m2^2, 64) n1) and of the long-K products (scattered /
+    // iterative: only the latter two).  Dense masked step: sized for each of its users -- PT1 (m1 x m1 over n1) and PT2 (m2 x m2 over
+    // n2) write slabs m_d^2 doubles, which exceeds n1 m2^2 on anisotropic inducing grids (m1 > ~22 m2) and on grids of a few long rows
+    w.Tcap = (w.scattered || w.iter) ? std::max<size_t>(256 * mmax2, 64 * n1)
+                                     : std::max({n1 * m2 * m2, (size_t)vg_longk_slabs((long)n1) * m1 * m1,
+                                                 (size_t)vg_longk_slabs((long)n2) * m2 * m2, std::min<size_t>(m2 * m2, 64) * n1});
+    w.T = a.take(w.Tcap);
     w.Tv = a.take((w.scattered || w.iter) ? 256 : n1 * m2 * m2);
     w.UB = a.take(m1 * n2); w.UV = a.take(m1 * n2); w.Zb = a.take(grid); w.Zv1 = a.take(grid); w.Zv2 = a.take(grid);
     w.B1s = a.take(m1 * n1); w.B2s = a.take(m2 * n2);
@@ -239,18 +244,28 @@ int gemm1(const double* A, long sa_m, long sa_k, const double* B, long sb_k, lon
     return VGGP_OK;
 }
 
+// slabs gemm_longk splits a reduction of length K into: K / 512, at most 256, none below K = 1024
+int vg_longk_slabs(long K) {
+    int ks = (int)std::min<long>(K / 512, 256);
+    if (ks < 2) return 1;
+    const int ktiles = (int)((K + VG_BK - 1) / VG_BK), per = (ktiles + ks - 1) / ks;          // (vg_gemm_add drops the empty splits)
+    return (ktiles + per - 1) / per;
+}
 // C (M x N, contiguous) = A B with a SHORT output and a LONG reduction (m x m results summed over 1e5 points): one workgroup per
 // tile would walk the whole K alone (5.8 ms at K = 100 000, measured), so the reduction is split over up to 256 workgroups whose
-// slabs are summed in fixed order.  scratch: >= 256 * M * N doubles.
+// slabs are summed in fixed order.  scratch holds scratch_doubles doubles: vg_longk_slabs(K) * M * N of them are written, and a
+// buffer that is shorter is refused before anything is launched.
 int gemm_longk(const double* A, long sa_m, long sa_k, const double* B, long sb_k, long sb_n, double* C, int M, int N, int K,
-               double* scratch, hipStream_t st) {
-    int ks = K / 512;
-    if (ks > 256) ks = 256;
+               double* scratch, size_t scratch_doubles, hipStream_t st) {
+    const int ks = vg_longk_slabs(K);
     if (ks < 2) return gemm1(A, sa_m, sa_k, B, sb_k, sb_n, C, N, M, N, K, st);
+    VG_REQUIRE((size_t)ks * M * N <= scratch_doubles,
+               "long-K product: M = %d, N = %d, K = %d needs %d slabs of M N doubles, but the scratch holds %zu doubles", M, N, K, ks,
+               scratch_doubles);
     VgGemmBatch g;
     vg_gemm_init(&g);
     const int ip = vg_gemm_add(&g, A, sa_m, sa_k, B, sb_k, sb_n, scratch, N, M, N, K, ks, (long)M * N);
-    const int slabs = g.p[ip].ksplit;
+    const int slabs = g.p[ip].ksplit;                                  // == ks
     VG_HIP(vg_gemm_launch(&g, st));
     VgRedBatch r;
     vg_red_init(&r);
@@ -357,8 +372,8 @@ int vgm_a0_terms(vggp_ctx* c, VgMasked& w, hipStream_t st) {
     VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * n1, st, B1, w.wn2, (int)m1, n1, w.B1s);
     VGM_LAUNCH1D(vgm_scalecols_kernel, m2 * n2, st, B2, w.wn1, (int)m2, n2, w.B2s);
     // (short outputs, long reductions: split-K with the T buffer -- free by now -- as slab scratch)
-    if ((rc = gemm_longk(w.B1s, n1, 1, B1, 1, n1, w.PT1, (int)m1, (int)m1, (int)n1, w.T, st))) return rc;
-    if ((rc = gemm_longk(w.B2s, n2, 1, B2, 1, n2, w.PT2, (int)m2, (int)m2, (int)n2, w.T, st))) return rc;
+    if ((rc = gemm_longk(w.B1s, n1, 1, B1, 1, n1, w.PT1, (int)m1, (int)m1, (int)n1, w.T, w.Tcap, st))) return rc;
+    if ((rc = gemm_longk(w.B2s, n2, 1, B2, 1, n2, w.PT2, (int)m2, (int)m2, (int)n2, w.T, w.Tcap, st))) return rc;
     return VGGP_OK;
 }
 
@@ -373,9 +388,9 @@ int vgs_projections(vggp_ctx* c, VgMasked& w, const double* y, hipStream_t st) {
     int rc;
     VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * N, st, B1, y, (int)m1, N, w.B1s);
     VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * N, st, V1, y, (int)m1, N, w.UV);           // (UV is free until the a0 stage)
-    if ((rc = gemm_longk(w.B1s, N, 1, B2, 1, N, C0, (int)m1, (int)m2, (int)N, w.T, st))) return rc;
-    if ((rc = gemm_longk(w.UV, N, 1, B2, 1, N, C1, (int)m1, (int)m2, (int)N, w.T, st))) return rc;
-    if ((rc = gemm_longk(w.B1s, N, 1, V2, 1, N, C2, (int)m1, (int)m2, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(w.B1s, N, 1, B2, 1, N, C0, (int)m1, (int)m2, (int)N, w.T, w.Tcap, st))) return rc;
+    if ((rc = gemm_longk(w.UV, N, 1, B2, 1, N, C1, (int)m1, (int)m2, (int)N, w.T, w.Tcap, st))) return rc;
+    if ((rc = gemm_longk(w.B1s, N, 1, V2, 1, N, C2, (int)m1, (int)m2, (int)N, w.T, w.Tcap, st))) return rc;
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B1, B1, (int)m1, N, w.nb1);
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B2, B2, (int)m2, N, w.nb2);
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, V1, B1, (int)m1, N, w.hv1);
@@ -398,8 +413,8 @@ int vgs_a0_terms(vggp_ctx* c, VgMasked& w, hipStream_t st) {
     VGM_LAUNCH1D(vgm_coldot_kernel, N, st, B1, w.UV, (int)m1, N, w.Zv2);
     VGM_LAUNCH1D(vgm_scalecols_kernel, m1 * N, st, B1, w.nb2, (int)m1, N, w.B1s);
     VGM_LAUNCH1D(vgm_scalecols_kernel, m2 * N, st, B2, w.nb1, (int)m2, N, w.B2s);
-    if ((rc = gemm_longk(w.B1s, N, 1, B1, 1, N, w.PT1, (int)m1, (int)m1, (int)N, w.T, st))) return rc;
-    if ((rc = gemm_longk(w.B2s, N, 1, B2, 1, N, w.PT2, (int)m2, (int)m2, (int)N, w.T, st))) return rc;
+    if ((rc = gemm_longk(w.B1s, N, 1, B1, 1, N, w.PT1, (int)m1, (int)m1, (int)N, w.T, w.Tcap, st))) return rc;
+    if ((rc = gemm_longk(w.B2s, N, 1, B2, 1, N, w.PT2, (int)m2, (int)m2, (int)N, w.T, w.Tcap, st))) return rc;
     return VGGP_OK;
 }
 
@@ -655,7 +670,7 @@ extern "C" int vggp_zgrad_scattered(vggp_ctx* c, const double* y, double* gz1, d
     for (int k = 0; k < 2; ++k) {
         VgDim& d = c->d[k];
         if (!pts[k]) continue;
-        if ((rc = gemm_longk(G[k], N, 1, d.BV, 1, N, WM[k], d.m, d.m, (int)N, w.T, st))) return rc;          // G_B B^T
+        if ((rc = gemm_longk(G[k], N, 1, d.BV, 1, N, WM[k], d.m, d.m, (int)N, w.T, w.Tcap, st))) return rc;          // G_B B^T
         VGM_LAUNCH1D(vgm_scal_kernel, (long)d.m * d.m, st, WM[k], (long)d.m * d.m, -0.5);
     }
     for (int pass = 0; pass < 2; ++pass) {

@@ -53,6 +53,7 @@ struct VgMasked {
     // the all-reduce buffer of the row-sharded masked step: [slack 2 m2^2 | C, C1, C2 (3 M) | wn2 (n1) | R3 (3 M^2)];
     // the collective covers everything after the slack (vg_partials_enqueue leaves G2, H2 in it, which this path ignores)
     double *mpay, *R3, *scal;
+    size_t Tcap = 0;               // doubles T holds (vgm_layout): what every gemm_longk on it is checked against
     void* mem = nullptr;
     size_t bytes = 0;
 };
@@ -99,7 +100,8 @@ int vgm_prepare(vggp_ctx* c, bool iter = false);
 int gemm1(const double* A, long sa_m, long sa_k, const double* B, long sb_k, long sb_n, double* C, int ldc, int M, int N, int K,
           hipStream_t st, double alpha = 1.0, int accum = 0);
 int gemm_longk(const double* A, long sa_m, long sa_k, const double* B, long sb_k, long sb_n, double* C, int M, int N, int K,
-               double* scratch, hipStream_t st);
+               double* scratch, size_t scratch_doubles, hipStream_t st);
+int vg_longk_slabs(long K);       // slabs gemm_longk writes for a reduction of length K (1: no split, no scratch)
 // what each of the four steps does once its arguments are non-null: no earlier step's state stays readable, theta is checked and kept
 int vgm_step_enter(vggp_ctx* c, const double theta[5]);
 int vgm_colstats(vggp_ctx* c, VgMasked& w, const double* W, hipStream_t st);
