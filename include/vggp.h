@@ -450,6 +450,37 @@ int vggp_set_inducing(vggp_ctx* ctx, int dim, const double* z, int64_t m);
 int vggp_posterior(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t ns,
                    double* mean, double* var, void* stream);
 
+/* posterior(x*) on a RASTER: the p1 x p2 cartesian grid of two coordinate axes, what every map of the reference evaluates
+ * (kronecker_structure.py:199-230 with X* built from a meshgrid).  g1 DEVICE [p1], g2 DEVICE [p2]; mean, var DEVICE [p1][p2], flat
+ * index a p2 + b; by definition the values the point-wise entry of the state gives at the points (g1[a], g2[b]).  On a raster the
+ * whitened factors are needed at the axis coordinates only, T_d = Q_d^T L0_d^-1 A_d(g_d) (q_d x p_d), and
+ *     mean = T1^T (Wm T2),      var = s1 s2 (1 + (T1 o T1)^T (Wv (T2 o T2)))
+ * with the compact weights of vggp_posterior: O(p1 p2 q1) in one fp64-MFMA launch (vggp_raster_contract below) instead of the
+ * O(p1 p2 q1 q2) of the point-wise contraction.  Reads the LAST finished step on the context, whichever kind it was:
+ *   vggp_elbo_step / vggp_elbo_finish   mean and variance; vggp_posterior's preamble (accurate recompute after a warm step, thin read-out)
+ *   vggp_elbo_step_masked / _scattered, vggp_elbo_step_masked_iter, vggp_elbo_step_scattered_iter
+ *                                       mean = (s1 s2 / sigma^2) U1^T A0 U2 from the state's m1 x m2 coefficients, U_d = L0_d^-1 A_d(g_d);
+ *                                       var must be NULL (VGGP_EINVAL before anything is launched: those variances t^T Sigma~^-1 t are no
+ *                                       Kronecker sums -- vggp_posterior_masked, vggp_posterior_masked_iter,
+ *                                       vggp_posterior_var_scattered_iter give them point by point)
+ * var = NULL: the mean only, on every state.  1 <= p_d <= 2^20; output indices are 64-bit.  Workspace (the context's lazy scratch):
+ * 2 m1 p1 + (2 m2 + 2 m1) p2 + m1^2 + m2^2 doubles after a full-grid step (the last two: W_d = Q_d^T L0_d^-1), 2 m1 p1 + (2 m2 + m1) p2
+ * after the other steps; nothing of size p1 p2.  VGGP_ESTATE without a finished step (the rules of the state's point-wise
+ * entry); VGGP_EINVAL on paired contexts.  Multi-rank contexts: as the state's point-wise entry (the state is replicated; after an
+ * iterative step the transport is verified and polled, no collective).  A raster call between two steps leaves the second step's bits
+ * unchanged wherever vggp_posterior does: after a cold or thin full-grid step and after the masked, scattered and iterative steps.  After a
+ * WARM full-grid step the first read-out of either kind runs the accurate recompute, which replaces the basis the next step starts from;
+ * the next step then returns the bits it returns after a vggp_posterior call in the raster call's place (both tested). */
+int vggp_posterior_raster(vggp_ctx* ctx, const double* g1, int64_t p1, const double* g2, int64_t p2, double* mean, double* var,
+                          void* stream);
+/* Its kernel as a building block, exported for tests, on caller-supplied DEVICE arrays: T1 [q][P1], U, Uv [q][P2], outputs [P1][P2],
+ *     mean[a][b] = sum_i T1[i][a] U[i][b],      var[a][b] = c0 + c1 sum_i T1[i][a]^2 Uv[i][b]
+ * One fp64-MFMA launch, 64 x 64 output tiles; the variance product's A fragment is the square of the mean product's, taken in
+ * registers; edges (P_d no multiple of 64, q no multiple of 4) are handled in the kernel, nothing is padded or copied.  var = NULL (Uv
+ * may then be NULL) skips the second product.  1 <= q, P1, P2 <= 2^20.  The context need not be planned. */
+int vggp_raster_contract(vggp_ctx* ctx, const double* T1, const double* U, const double* Uv, int64_t q, int64_t P1, int64_t P2,
+                         double c0, double c1, double* mean, double* var, void* stream);
+
 /* Dense ns x ns covariance of posterior(x*) (DEVICE [ns][ns]; ns <= 8192 and M ns <= 2^27): K** + Kuf*^T Sigma^-1 Kuf* -
  * Kuf*^T Kuu^-1 Kuf*, kronecker_structure.py:223-229, from the step's eigenbasis (never forming Sigma); the masked variant
  * from the dense Sigma~^-1 of the last masked / scattered step.  Callers that only need the diagonal use vggp_posterior.

@@ -87,6 +87,8 @@ SYMBOLS = {
     "vggp_zgrad_scattered": (_I, [_P, _P, _P, _P, _P]),
     "vggp_set_inducing": (_I, [_P, C.c_int, _P, C.c_int64]),
     "vggp_posterior": (_I, [_P, _P, _P, _I64, _P, _P, _P]),
+    "vggp_posterior_raster": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "vggp_raster_contract": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _D, _D, _P, _P, _P]),
     "vggp_readout": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I, _P]),
     "vggp_readout_masked": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I, _P]),
     "vggp_posterior_masked": (_I, [_P, _P, _P, _I64, _P, _P, _P]),

@@ -427,7 +427,7 @@ static int trsm_inplace(const double* L, long m, long ldl, const double* Dinv, d
 // and the range eigenpairs of a thin step are exact Ritz pairs of G on span(V1) = range(G) -- consistent (eigenvalue, eigenvector)
 // pairs, unlike the projected-off complement rows of the full warm chain whose mixtures made the cold recompute necessary
 // (DESIGN.md section 2).  VGGP_NO_THIN_READOUT=1: recompute cold as after any warm step.
-static bool vg_thin_readout(const vggp_ctx* c) {
+bool vg_thin_readout(const vggp_ctx* c) {
     static const bool off = getenv("VGGP_NO_THIN_READOUT") != nullptr;
     return !off && c->have_step && c->last_thin && !c->acc_valid;
 }

@@ -43,6 +43,8 @@ struct VgGraphKey {
 
 typedef VgHostOut HostOut;   // pinned readback block (common.h)
 
+enum { VG_LAST_NONE = 0, VG_LAST_FULL, VG_LAST_DENSE, VG_LAST_ITER };      // vggp_ctx::last_kind
+
 struct vggp_ctx {
     int device = 0;
     bool planned = false;
@@ -63,6 +65,7 @@ struct vggp_ctx {
     int gh_slabs[2] = {1, 1}, cc_slabs = 1;      // split-K slab counts actually produced by the last partials launch
     long payload_len = 0;
     bool have_partials = false, have_step = false, have_masked = false;
+    int last_kind = 0;               // VG_LAST_*: which kind of step finished last (vggp_posterior_raster reads "the last step, whichever kind")
     bool have_iter = false;          // the last finished step was a successful vggp_elbo_step_masked_iter / vggp_elbo_step_scattered_iter
                                      // (which of the two: the plan's VGGP_FLAG_SCATTERED; their read-outs: iter_readout.hip)
     void* masked = nullptr;          // VgMasked workspace (mspace_ws.h), allocated on first use
@@ -150,6 +153,7 @@ int vg_ensure_misc(vggp_ctx* c, size_t bytes);
 int vg_quiesce(vggp_ctx* c);
 void vg_graphs_clear(vggp_ctx* c);                       // drop every captured step graph (re-planning)
 int vg_accurate_state(vggp_ctx* c, hipStream_t st);      // read-outs after a warm step: re-run the finish half cold on the resident G, H, C
+bool vg_thin_readout(const vggp_ctx* c);                 // api.hip: the read-outs come straight from the last (thin) step's range directions
 // the partials half.  early: 1 = thin chain, 2 = regular warm chains ([C;C1;C2] is then the first rider of the eigensolver chain)
 struct VgPartials { bool reduce = true, extrap = false, fused = false, apply_ns = false; int early = 0; };
 int vg_partials_enqueue(vggp_ctx* c, const double* Y, double* payload, hipStream_t st, const VgPartials& o = VgPartials());

@@ -558,6 +558,7 @@ static int vgi_finish(vggp_ctx* c, VgMasked& w, const VgIter& it, const char* wh
     if (c->h_out->counters[1][3]) { vg_set_error("iterative %s step: the Lanczos quadrature failed (code %d)", what, c->h_out->counters[1][3]); return VGGP_ENOCONV; }
     vgi_basis_done(w, iters);
     c->have_step = false; c->have_partials = false;
+    c->last_kind = VG_LAST_ITER;
     c->have_iter = true;             // a0, the factors and the preconditioner's basis are there for the iterative read-outs
     return VGGP_OK;
 }

@@ -488,6 +488,7 @@ static int vgm_finish(vggp_ctx* c, VgMasked& w, const char* what, const VgmRedAr
     }
     if (status) { vg_set_error("%s step: a factor is not positive definite", what); return VGGP_ENOTPD; }
     c->have_masked = true;
+    c->last_kind = VG_LAST_DENSE;
     return VGGP_OK;
 }
 

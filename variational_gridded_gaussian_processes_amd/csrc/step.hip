@@ -1196,6 +1196,7 @@ static int finish_collect(vggp_ctx* c, double* elbo_out, double grad_out[5], vgg
     }
     if (++c->warm_run >= 512) vg_drop_warm(c);                 // periodic cold restart: bounds the drift of orthogonality
     c->have_step = true;
+    c->last_kind = VG_LAST_FULL;
     return VGGP_OK;
 }
 

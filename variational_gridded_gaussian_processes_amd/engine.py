@@ -578,6 +578,38 @@ class Engine:
         check(getattr(self.lib, _fn)(self._h, _ptr(xs1), _ptr(xs2), ns, _ptr(mean), _ptr(var), _stream(self.device)))
         return mean, var
 
+    def posterior_raster(self, g1: torch.Tensor, g2: torch.Tensor, want_var: bool = True):
+        """posterior(x*) on the cartesian grid of two coordinate axes (vggp_posterior_raster): g1 [p1], g2 [p2] -> (mean [p1, p2],
+        var [p1, p2] or None), element (a, b) at the point (g1[a], g2[b]).  Reads the last finished step, whichever kind; the masked,
+        scattered and iterative states give the mean only (want_var=True raises there: use their point-wise read-outs)."""
+        a1 = torch.as_tensor(g1).to(self.device, torch.float64).reshape(-1).contiguous()
+        a2 = torch.as_tensor(g2).to(self.device, torch.float64).reshape(-1).contiguous()
+        p1, p2 = a1.numel(), a2.numel()
+        mean = torch.empty(p1, p2, dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mean) if want_var else None
+        check(self.lib.vggp_posterior_raster(self._h, _ptr(a1), p1, _ptr(a2), p2, _ptr(mean), _ptr(var), _stream(self.device)))
+        return mean, var
+
+    def raster_contract(self, T1: torch.Tensor, U: torch.Tensor, Uv: Optional[torch.Tensor] = None, c0: float = 0.0, c1: float = 1.0,
+                        out: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None):
+        """The raster kernel on its own (vggp_raster_contract): T1 [q, P1], U [q, P2], Uv [q, P2] or None -> (mean [P1, P2] = T1^T U,
+        var [P1, P2] = c0 + c1 (T1 o T1)^T Uv or None).  out: (mean, var) views to write into instead of fresh tensors.  Operands and
+        outputs must be contiguous float64 GPU tensors (TypeError otherwise: the kernel receives their pointers)."""
+        q, P1 = T1.shape
+        P2 = U.shape[1]
+        if U.shape[0] != q or (Uv is not None and tuple(Uv.shape) != (q, P2)):
+            raise ValueError("raster_contract: T1 [q, P1], U [q, P2], Uv [q, P2]")
+        if out is None:
+            mean = torch.empty(P1, P2, dtype=torch.float64, device=self.device)
+            var = torch.empty_like(mean) if Uv is not None else None
+        else:
+            mean, var = out
+            if tuple(mean.shape) != (P1, P2) or (var is not None and tuple(var.shape) != (P1, P2)):
+                raise ValueError("raster_contract: out tensors must be [P1, P2]")
+        check(self.lib.vggp_raster_contract(self._h, _ptr(T1), _ptr(U), _ptr(Uv), q, P1, P2, float(c0), float(c1), _ptr(mean), _ptr(var),
+                                            _stream(self.device)))
+        return mean, var
+
     # -- exact GP (dense N x N, N <= 16384; a workspace of its own beside the planned model) --------------
     def exact_plan(self, kind1: str, kind2: str, x1, x2) -> None:
         """Exact GP on the N points (x1[k], x2[k]) with kernel_1 * kernel_2 of the given kinds (vggp_exact_plan).  Independent of

@@ -535,6 +535,38 @@ class KroneckerStructure(torch.nn.Module):
         return MultivariateNormal(p.mean, p.variance + noise,
                                   cov_fn=lambda: p.covariance_matrix + noise * torch.eye(p.mean.shape[0], dtype=p.variance.dtype))
 
+    def posterior_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor) -> MultivariateNormal:
+        """posterior(torch.cartesian_prod(x1_star, x2_star)) for a map: the raster of two coordinate axes (the meshgrid cells of the
+        reference's notebooks), flat index a * P2 + b.  Mean and variance come from Engine.posterior_raster, O(P1 P2 m) instead of
+        O(P1 P2 m^2); there is no dense covariance (`.covariance_matrix` raises).  On a grid with holes, on scattered points and on the
+        iterative solvers the raster entry gives the mean; the variance then comes from that state's point-wise route (posterior()), on
+        the first use of `.variance`."""
+        self._refresh()
+        a1 = torch.as_tensor(x1_star, dtype=torch.float64).reshape(-1)
+        a2 = torch.as_tensor(x2_star, dtype=torch.float64).reshape(-1)
+        if self._engine.paired:
+            raise NotImplementedError(f"{type(self).__name__}: posterior_grid needs Kronecker inducing features; paired inducing points "
+                                      f"have none -- use posterior(torch.cartesian_prod(x1_star, x2_star))")
+
+        def no_cov():
+            raise NotImplementedError("posterior_grid has no dense covariance (a raster of P1 P2 points); use .variance, or posterior() "
+                                      "on a few points for its .covariance_matrix")
+        if not (self._masked or self._scattered):
+            mean, var = self._engine.posterior_raster(a1, a2)
+            return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(), cov_fn=no_cov)
+        mean, _ = self._engine.posterior_raster(a1, a2, want_var=False)
+
+        def var():                       # (posterior() refreshes the state itself; means-only scattered models raise here as there)
+            return self.posterior(torch.cartesian_prod(a1, a2)).variance
+        return MultivariateNormal(mean.reshape(-1).cpu(), var, cov_fn=no_cov)
+
+    def posterior_predictive_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor) -> MultivariateNormal:
+        """posterior_grid with the likelihood's noise variance added (kronecker_structure.py:232-247 on a raster)."""
+        p = self.posterior_grid(x1_star, x2_star)
+        noise = self.likelihood.noise.detach().to(torch.float64)
+        variance = p._variance
+        return MultivariateNormal(p.mean, (lambda: p.variance + noise) if callable(variance) else variance + noise, cov_fn=p._cov_fn)
+
     # -- dense views kept for small sizes / debugging (the hot path never forms them) ------------------------------
     def _factor(self, d: int, x: torch.Tensor):
         """Unit-outputscale per-dimension factors from the engine: A0 (m x n at coordinates x), K0 (m x m)."""
