@@ -481,6 +481,58 @@ int vggp_posterior_raster(vggp_ctx* ctx, const double* g1, int64_t p1, const dou
 int vggp_raster_contract(vggp_ctx* ctx, const double* T1, const double* U, const double* Uv, int64_t q, int64_t P1, int64_t P2,
                          double c0, double c1, double* mean, double* var, void* stream);
 
+/* Joint (correlated) samples of posterior(x*) on a raster: n_samples realisations of f on the p1 x p2 cartesian grid of the axes g1, g2
+ * (DEVICE [p1], [p2]), what `.sample()` gives on the MultivariateNormal the reference's posterior() returns for X* = cartesian_prod(g1, g2)
+ * (kronecker_structure.py:199-230), without any p1 p2 x p1 p2 matrix.  With the state of the last finished step -- L0_d, theta, and X_s the
+ * whitened coefficient draw of the vggp_qv_sample* entries above, Cov(vec X_s) = Sigma~^-1, produced by the very same stage --
+ *     U_d = L0_d^-1 A0_d(g_d),  B_d = sqrt(s_d) U_d  (m_d x p_d),     k_d = the unit POINT kernel of dimension d on its axis (p_d x p_d),
+ *     r_d = k_d - U_d^T U_d,     C_d = chol(r_d + eta I),     Kc2 = chol(k_2 + eta I),     eta = 1e-8 (a fixed nugget at unit outputscale),
+ *     F_s = mu + B1^T W_s + sqrt(s1 s2) C1 T_s,     W_s = X_s B2 + sqrt(s2) H_s C2^T  (m1 x p2),     T_s = G_s Kc2^T  (p1 x p2),
+ * mu = the mean vggp_posterior_raster returns in the same state, G_s [p1][p2] and H_s [m1][p2] standard normals, so that
+ *     Cov(vec F_s) = (B1 (x) B2)^T Sigma~^-1 (B1 (x) B2) + s1 s2 (r1 + eta I) (x) (k2 + eta I) + (B1^T B1) (x) s2 (r2 + eta I)
+ * = K** + Kuf*^T Sigma^-1 Kuf* - Kuf*^T Kuu^-1 Kuf* (:223-229) plus the nugget terms (about 2 eta s1 s2 of extra variance): the prior
+ * residual k1 (x) k2 - q1 (x) q2 = (k1 - q1) (x) k2 + q1 (x) (k2 - q2) is a sum of two PSD Kronecker products.  Cost per sample
+ * 2 m1 m2 p2 + 2 m1 p2^2 + p1 p2^2 + 2 m1 p1 p2 + p1^2 p2 flops; the roots (per call, nothing is cached) are three p_d x p_d Cholesky
+ * factorisations by vggp_cholesky_inverse, its jitter schedule on top of the nugget: info->jitter1 = the level C1 took, info->jitter2 =
+ * the larger of C2's and Kc2's (0 on every tested problem); VGGP_ENOTPD when a root fails every level.
+ * Noise.  eps_u [n_samples][m1][m2] (E) and, on the iterative entries, eps_obs (F) as the vggp_qv_sample* entries; eps_g DEVICE
+ * [n_samples][p1][p2] is G, eps_h DEVICE [n_samples][m1][p2] is H.  Either ALL of an entry's noise arrays are given, or all are NULL and
+ * the noise is generated on the device from (seed, first): streams 0 and 1 as above and
+ *       G  stream 2, idx = s p1 p2 + a p2 + b;     H  stream 3, idx = s m1 p2 + i p2 + b;     s = first + local sample.
+ * Sample s of a seed is the same numbers whatever n_samples, block or call asks for it (to 1e-12), and it uses the E_s of sample s of
+ * vggp_qv_sample* with that seed: the two are one joint draw.  Zero noise returns mu bit for bit.
+ *   out   DEVICE [n_samples][p1][p2], flat index a p2 + b
+ * Samples are processed in blocks of min(64, block, n_samples) samples, fewer when the block's p1 x p2 scratch would pass 1 GiB (one
+ * sample if a single map is larger); G is generated into `out`.  The number of launches of a block does not depend on the samples in
+ * it.  Iterative entries: W, n_obs, tol, max_iter, block, info->rounds1 / sweeps1 as vggp_qv_sample_*_iter (one block solve per block
+ * of samples).  Workspace (the context's own, kept): p1 p2 + 2 m1 p1 + 2 m2 p2 + 2 p1^2 + 3 p2^2 + max(p1, p2)^2 + nbc (2 m1 p2 + p1 p2)
+ * doubles, plus 2 nbc m1 m2 on a full grid.
+ * State rules: those of the matching vggp_qv_sample* entry (the full-grid entry: after vggp_elbo_step / vggp_elbo_finish; it takes mu
+ * first, then the accurate state as vggp_qv_sample does); a call between two steps leaves the next step's bits unchanged wherever
+ * that entry does.  VGGP_EINVAL before anything is launched or written: paired contexts; a dimension with VGGP_BASIS_B1 (its residual
+ * k_d - q_d is indefinite: that covariance is no Schur complement); multi-rank contexts; p_d < 1 or p_d > 8192 (the Cholesky's limit);
+ * n_samples < 1; first < 0; NULL out or axes; only some of the noise arrays; block > 64. */
+int vggp_posterior_raster_sample(vggp_ctx* ctx, const double* g1, int64_t p1, const double* g2, int64_t p2, int64_t n_samples, uint64_t seed,
+                                 int64_t first, const double* eps_u, const double* eps_g, const double* eps_h, double* out, vggp_info* info,
+                                 void* stream);
+int vggp_posterior_raster_sample_masked_iter(vggp_ctx* ctx, const double* g1, int64_t p1, const double* g2, int64_t p2, const double* W,
+                                             double n_obs, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u,
+                                             const double* eps_obs, const double* eps_g, const double* eps_h, double tol, int max_iter,
+                                             int block, double* out, vggp_info* info, void* stream);
+int vggp_posterior_raster_sample_scattered_iter(vggp_ctx* ctx, const double* g1, int64_t p1, const double* g2, int64_t p2, int64_t n_samples,
+                                                uint64_t seed, int64_t first, const double* eps_u, const double* eps_obs, const double* eps_g,
+                                                const double* eps_h, double tol, int max_iter, int block, double* out, vggp_info* info,
+                                                void* stream);
+/* Their last kernel as a building block, exported for tests, on caller-supplied DEVICE arrays: B1 [q][P1], Wt [S][q][P2], C1 [P1][P1]
+ * lower triangular, Tt [S][P1][P2], mean [P1][P2] or NULL, out [S][P1][P2]:
+ *     out[s][a][b] = mean[a][b] + sum_i B1[i][a] Wt[s][i][b] + c sum_{a' <= a} C1[a][a'] Tt[s][a'][b]
+ * One fp64-MFMA launch for all samples, 64 x 64 output tiles; both products accumulate in the same registers; the triangular product's
+ * k-range ends at the tile's last row, and nothing above the diagonal of C1 is read (NaN included); c = 0 skips that product; edges are
+ * handled in the kernel, nothing is padded or copied; output indices are 64-bit.  1 <= q, P1, P2 <= 2^20, 1 <= S <= 65535.  The
+ * context need not be planned. */
+int vggp_raster_sample_contract(vggp_ctx* ctx, const double* B1, const double* Wt, const double* C1, const double* Tt, int64_t S, int64_t q,
+                                int64_t P1, int64_t P2, double c, const double* mean, double* out, void* stream);
+
 /* Dense ns x ns covariance of posterior(x*) (DEVICE [ns][ns]; ns <= 8192 and M ns <= 2^27): K** + Kuf*^T Sigma^-1 Kuf* -
  * Kuf*^T Kuu^-1 Kuf*, kronecker_structure.py:223-229, from the step's eigenbasis (never forming Sigma); the masked variant
  * from the dense Sigma~^-1 of the last masked / scattered step.  Callers that only need the diagonal use vggp_posterior.

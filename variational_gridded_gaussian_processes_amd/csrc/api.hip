@@ -106,6 +106,7 @@ extern "C" int vggp_destroy(vggp_ctx* c) {
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     if (c->arena) (void)hipFree(c->arena);
     if (c->misc) (void)hipFree(c->misc);
+    if (c->rs_mem) (void)hipFree(c->rs_mem);
     if (c->h_theta) (void)hipHostFree(c->h_theta);
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->ticket) (void)hipFree(c->ticket);
@@ -551,6 +552,26 @@ extern "C" int vggp_qv_cov(vggp_ctx* c, double* cov, void* stream) {
     return VGGP_OK;
 }
 
+// The coefficient draw of the full-grid samplers (vggp_qv_sample, vggp_posterior_raster_sample), one block of up to nbc samples on the
+// interleaved layout [m1][nbc][m2]:  Xa = (Q1^T E Q2) o D^-1/2, the eigenbasis coordinates of X_s = Sigma~^-1/2 E_s (cn live columns,
+// E from eps or stream 0 at sample s0).  Two GEMMs and two elementwise kernels; Xb is scratch of the same size.  After vg_accurate_state.
+int vg_sample_full_coeffs(vggp_ctx* c, const double* eps, unsigned long long seed, unsigned long long s0, int nbc, int cn, double* Xa, double* Xb,
+                          hipStream_t st) {
+    const long m1 = c->desc.m1, m2 = c->desc.m2;
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    const int wide = nbc * (int)m2, tall = (int)m1 * nbc;
+    VgGemmBatch g;
+    VG_HIP(vg_sample_block_noise_launch(Xa, eps, seed, s0, (int)m1, nbc, (int)m2, cn, st));
+    vg_gemm_init(&g);
+    vg_gemm_add(&g, d1.QtPrev, m1, 1, Xa, wide, 1, Xb, wide, (int)m1, wide, (int)m1);                // Q1^T E    (rows of QtPrev = eigenvectors)
+    VG_HIP(vg_gemm_launch(&g, st));
+    vg_gemm_init(&g);
+    vg_gemm_add(&g, Xb, m2, 1, d2.QtPrev, 1, m2, Xa, (int)m2, tall, (int)m2, (int)m2);               // (.) Q2
+    VG_HIP(vg_gemm_launch(&g, st));
+    VG_HIP(vg_sample_root_scale_launch(Xa, c->invD, (int)m1, nbc, (int)m2, st));                     // o D^-1/2
+    return VGGP_OK;
+}
+
 // Joint samples of q(v) of the last full-grid step, without the M x M covariance.  Sigma~ = I + rho Phi is diagonal in the kept
 // Kronecker eigenbasis, D = 1 + rho lam1 lam2^T, so with E_s standard normal over the cells
 //     V_s = mean + sqrt(s1^e1 s2^e2) L0_1 X_s L0_2^T,   X_s = Sigma~^-1/2 E_s = Q1 ((Q1^T E_s Q2) o D^-1/2) Q2^T
@@ -593,11 +614,8 @@ extern "C" int vggp_qv_sample(vggp_ctx* c, int64_t n_samples, uint64_t seed, int
     };
     for (int64_t off = 0; off < n_samples; off += nbc) {
         const int cn = (int)std::min<int64_t>(nbc, n_samples - off);
-        VG_HIP(vg_sample_block_noise_launch(Xa, eps_u ? eps_u + off * M : nullptr, seed, (unsigned long long)(first + off), (int)m1, nbc, (int)m2, cn,
-                                            st));
-        VG_HIP(gemm(d1.QtPrev, m1, 1, Xa, wide, 1, Xb, wide, (int)m1, wide, (int)m1));               // Q1^T E    (rows of QtPrev = eigenvectors)
-        VG_HIP(gemm(Xb, m2, 1, d2.QtPrev, 1, m2, Xa, (int)m2, tall, (int)m2, (int)m2));              // (.) Q2
-        VG_HIP(vg_sample_root_scale_launch(Xa, c->invD, (int)m1, nbc, (int)m2, st));                 // o D^-1/2
+        if ((rc = vg_sample_full_coeffs(c, eps_u ? eps_u + off * M : nullptr, seed, (unsigned long long)(first + off), nbc, cn, Xa, Xb, st)))
+            return rc;                                                                                // (Q1^T E Q2) o D^-1/2
         VG_HIP(gemm(Xa, m2, 1, d2.RQ, 1, m2, Xb, (int)m2, tall, (int)m2, (int)m2));                  // (.) (L0_2 Q2)^T
         VG_HIP(gemm(d1.RQ, m1, 1, Xb, wide, 1, Xa, wide, (int)m1, wide, (int)m1));                   // (L0_1 Q1) (.)
         VG_HIP(vg_sample_out_launch(Xa, mean, c->theta, e1, e2, (int)m1, nbc, (int)m2, cn, out + off * M, st));

@@ -80,6 +80,8 @@ struct vggp_ctx {
     // scratch for the exported building blocks / posterior (lazy)
     void* misc = nullptr;
     size_t misc_bytes = 0;
+    void* rs_mem = nullptr;           // workspace of the raster samples (raster_sample.hip): apart from misc, which the roots' Cholesky uses
+    size_t rs_bytes = 0;
     double* sumsq_partial = nullptr;
     double* sumsq_out = nullptr;
     // captured step graphs.  Capture is illegal on the legacy default stream, so when the caller passes stream 0 the
@@ -229,6 +231,16 @@ hipError_t vg_sample_fuse_launch(double* Z, const double* K, const double* theta
 hipError_t vg_sample_root_scale_launch(double* X, const double* invD, int m1, int nbc, int m2, hipStream_t st);           // X o= sqrt(invD)
 hipError_t vg_sample_out_launch(const double* Y, const double* mean, const double* theta, int e1, int e2, int m1, int nbc, int m2, int cn,
                                 double* out, hipStream_t st);                                                            // out[c] = mean + sqrt(s1^e1 s2^e2) Y[:, c, :]
+// the same noise kernels on any stream of the generator (raster samples): rows [m1][nbc][w] from eps[c][a][b] or idx = (s0 + c) m1 w + a w + b
+hipError_t vg_sample_rows_noise_launch(double* E, const double* eps, unsigned long long seed, unsigned stream_id, unsigned long long s0, int m1,
+                                       int nbc, long w, int cn, hipStream_t st);
+// x[i] *= sqrt(s1 s2) for i < n  (theta: the device hyper-parameters)
+hipError_t vg_sample_scale_root_launch(double* x, long n, const double* theta, hipStream_t st);
+// A[i][i] += eta (p x p)
+hipError_t vg_sample_nugget_launch(double* A, long p, double eta, hipStream_t st);
+// the coefficient draw of the full-grid samplers (api.hip): Xa [m1][nbc][m2] = (Q1^T E Q2) o D^-1/2; Xb: scratch of the same size
+int vg_sample_full_coeffs(vggp_ctx* c, const double* eps, unsigned long long seed, unsigned long long s0, int nbc, int cn, double* Xa, double* Xb,
+                          hipStream_t st);
 // batch of triangular solves, each in place on its X (api.hip: element (row k, column c) at X[k * sk + c * sc])
 #define VG_TRSM_BLK 128
 struct VgTrsmSpec {

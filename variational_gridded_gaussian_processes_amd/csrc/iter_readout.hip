@@ -325,18 +325,49 @@ extern "C" int vggp_posterior_var_scattered_iter(vggp_ctx* c, const double* xs1,
 // products work on the interleaved layout [m1][nbc][m2], one GEMM each, so a sample's bits do not depend on its block.  The noise is
 // the caller's (eps_u, eps_obs) or the counter-based generator's (sample.hip).  Specification: tests/qv_sample_spec.py.
 // ================================================================================================================================
-static int vgi_sample_run(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, int64_t n_samples, uint64_t seed,
-                          int64_t first, const double* eps_u, const double* eps_obs, double tol, int max_iter, int block, double* out,
-                          vggp_info* info, void* stream) {
+// What the samplers of an iterative state check before anything is launched (vggp_qv_sample_*_iter, vggp_posterior_raster_sample_*_iter):
+// the context and its plan kind, W / n_obs, the sample arguments (noise_ok: the entry's own all-or-none rule over its noise arrays), a
+// finished iterative step; then the defaults of block, tol, max_iter and a zeroed info
+int vgi_sample_enter(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, int64_t n_samples, int64_t first, const void* out,
+                     bool noise_ok, const char* noise_rule, double* tol, int* max_iter, int* block, vggp_info* info) {
     if (c && c->planned && !c->is_paired)
         VG_REQUIRE(!vgi_multi(c), "%s: joint samples run on single-rank contexts only (this context is multi-rank)", fn);
     int rc = vgi_readout_enter(c, fn, scattered, /*gridded=*/false, "plan the context with VGGP_FLAG_SCATTERED", "the context was planned for scattered points",
-                               "bad argument", W, n_obs, block);
+                               "bad argument", W, n_obs, *block);
     if (rc) return rc;
     VG_REQUIRE(n_samples >= 1 && n_samples < (1LL << 31), "%s: n_samples = %lld must be at least 1", fn, (long long)n_samples);
     VG_REQUIRE(first >= 0 && out, "%s: bad argument", fn);
-    VG_REQUIRE((eps_u == nullptr) == (eps_obs == nullptr), "%s: eps_u and eps_obs are either both NULL (generated noise) or both given", fn);
-    if ((rc = vgi_readout_defaults(c, fn, scattered, &block, &tol, &max_iter, info))) return rc;
+    VG_REQUIRE(noise_ok, "%s: %s", fn, noise_rule);
+    return vgi_readout_defaults(c, fn, scattered, block, tol, max_iter, info);
+}
+// the read-outs' workspace for blocks of nbc samples (qv_mean: room for the q(v) mean in r.mean)
+int vgi_sample_prepare(vggp_ctx* c, VgReadout& r, int nbc, const double* W, double n_obs, bool qv_mean, hipStream_t st) {
+    return vgi_readout_prepare(c, *reinterpret_cast<VgMasked*>(c->masked), r, nbc, false, W, n_obs, st, /*sample=*/qv_mean);
+}
+// The coefficient draw of the samplers of an iterative state, one block of nbc columns (cn live, first sample s0):
+//     Z_s = E_s + sqrt(rho) K F_s,   X_s = Sigma~^-1 Z_s   by ONE block PCG solve  ->  r.it.X  [m1][nbc][m2]
+// (E: eps_u or stream 0, F: eps_obs or stream 1; both point at the block's first sample)
+int vgi_sample_coeffs(vggp_ctx* c, VgReadout& r, const char* fn, bool scattered, const double* eps_u, const double* eps_obs, uint64_t seed,
+                      unsigned long long s0, int cn, double tol, int max_iter, int* solves, int* max_its, vggp_info* info, hipStream_t st) {
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgDim &d1 = c->d[0], &d2 = c->d[1];
+    VgIter& it = r.it;
+    const int m1 = w.m1, m2 = w.m2, nbc = it.nbc;
+    const long n1 = w.n1, n2 = w.n2, nb = w.M * nbc;
+    int rc;
+    VG_HIP(vg_sample_block_noise_launch(r.T, eps_u, seed, s0, m1, nbc, m2, cn, st));
+    VG_HIP(vg_sample_field_noise_launch(it.F0, scattered ? nullptr : it.Wt, eps_obs, seed, s0, n1, nbc, n2, cn, st));
+    if (scattered) VG_HIP(vg_kr_back_launch(d1.BV, d2.BV, it.F0, m1, m2, n1, nbc, it.AP, it.krs, st));
+    else if ((rc = vgi_back(w, it, d1.BV, it.F0, d2.BV, it.AP, st))) return rc;
+    VG_HIP(vg_sample_fuse_launch(r.T, it.AP, c->theta, nb, st));                                               // Z = E + sqrt(rho) K F
+    return vgi_solve_block(c, w, r, fn, tol, max_iter, solves, max_its, info, st);
+}
+static int vgi_sample_run(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, int64_t n_samples, uint64_t seed,
+                          int64_t first, const double* eps_u, const double* eps_obs, double tol, int max_iter, int block, double* out,
+                          vggp_info* info, void* stream) {
+    int rc = vgi_sample_enter(c, fn, scattered, W, n_obs, n_samples, first, out, (eps_u == nullptr) == (eps_obs == nullptr),
+                              "eps_u and eps_obs are either both NULL (generated noise) or both given", &tol, &max_iter, &block, info);
+    if (rc) return rc;
     VG_ENTER_DEVICE(c->device);
     hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
@@ -346,21 +377,15 @@ static int vgi_sample_run(vggp_ctx* c, const char* fn, bool scattered, const dou
     const long nodes = scattered ? n1 : n1 * n2;
     const int nbc = (int)std::min<int64_t>(block, n_samples);
     VgReadout r;
-    if ((rc = vgi_readout_prepare(c, w, r, nbc, false, W, n_obs, st, /*sample=*/true))) return rc;
+    if ((rc = vgi_sample_prepare(c, r, nbc, W, n_obs, /*qv_mean=*/true, st))) return rc;
     VgIter& it = r.it;
     if ((rc = vgi_qv_mean(c, w, r.mean, st))) return rc;
-    const long nb = M * nbc;
     int max_its = 0, solves = 0;
     for (int64_t off = 0; off < n_samples; off += nbc) {
         const int cn = (int)std::min<int64_t>(nbc, n_samples - off);
-        const unsigned long long s0 = (unsigned long long)(first + off);
-        VG_HIP(vg_sample_block_noise_launch(r.T, eps_u ? eps_u + off * M : nullptr, seed, s0, m1, nbc, m2, cn, st));
-        VG_HIP(vg_sample_field_noise_launch(it.F0, scattered ? nullptr : it.Wt, eps_obs ? eps_obs + off * nodes : nullptr, seed, s0, n1, nbc, n2, cn,
-                                            st));
-        if (scattered) VG_HIP(vg_kr_back_launch(d1.BV, d2.BV, it.F0, m1, m2, n1, nbc, it.AP, it.krs, st));
-        else if ((rc = vgi_back(w, it, d1.BV, it.F0, d2.BV, it.AP, st))) return rc;
-        VG_HIP(vg_sample_fuse_launch(r.T, it.AP, c->theta, nb, st));                                               // Z = E + sqrt(rho) K F
-        if ((rc = vgi_solve_block(c, w, r, fn, tol, max_iter, &solves, &max_its, info, st))) return rc;
+        if ((rc = vgi_sample_coeffs(c, r, fn, scattered, eps_u ? eps_u + off * M : nullptr, eps_obs ? eps_obs + off * nodes : nullptr, seed,
+                                    (unsigned long long)(first + off), cn, tol, max_iter, &solves, &max_its, info, st)))
+            return rc;
         if ((rc = gemm1(d1.L0, m1, 1, it.X, (long)nbc * m2, 1, it.Tm, nbc * m2, m1, nbc * m2, m1, st))) return rc;     // L0_1 X
         if ((rc = gemm1(it.Tm, m2, 1, d2.L0, 1, m2, it.Tm2, m2, m1 * nbc, m2, m2, st))) return rc;                     // (.) L0_2^T
         VG_HIP(vg_sample_out_launch(it.Tm2, r.mean, c->theta, e1, e2, m1, nbc, m2, cn, out + off * M, st));

@@ -110,6 +110,16 @@ int vgs_projections(vggp_ctx* c, VgMasked& w, const double* y, hipStream_t st);
 int vgs_a0_terms(vggp_ctx* c, VgMasked& w, hipStream_t st);
 // ---- masked_readout.hip (vg_whitened_columns, vg_whitened_cross: ctx.h) ------------------------------------------------
 int vgi_qv_mean(vggp_ctx* c, VgMasked& w, double* mean, hipStream_t st);
+// ---- iter_readout.hip: the stages the samplers of an iterative state share (joint samples of q(v), raster samples) ----
+int vgi_sample_enter(vggp_ctx* c, const char* fn, bool scattered, const double* W, double n_obs, int64_t n_samples, int64_t first, const void* out,
+                     bool noise_ok, const char* noise_rule, double* tol, int* max_iter, int* block, vggp_info* info);
+int vgi_sample_prepare(vggp_ctx* c, VgReadout& r, int nbc, const double* W, double n_obs, bool qv_mean, hipStream_t st);
+int vgi_sample_coeffs(vggp_ctx* c, VgReadout& r, const char* fn, bool scattered, const double* eps_u, const double* eps_obs, uint64_t seed,
+                      unsigned long long s0, int cn, double tol, int max_iter, int* solves, int* max_its, vggp_info* info, hipStream_t st);
+// ---- raster.hip: the raster mean of the last step (full-grid state: mean and, with var, variance), axis factor columns A_d = a_d(g_d) ----
+int vg_raster_factors(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* A1, double* A2, hipStream_t st);
+int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, double* var, hipStream_t st);
+int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st);
 // ---- iter_step.hip ---------------------------------------------------------------------------------------------------
 __global__ void vgi_transpose_kernel(const double* W, long n1, long n2, double* Wt);
 __global__ void vgi_mul_kernel(const double* a, const double* b, long n, double* out);

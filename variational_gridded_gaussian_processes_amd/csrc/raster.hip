@@ -128,7 +128,7 @@ __global__ void vg_raster_rho_kernel(double* x, long n, const double* theta) {
 }
 
 // factor columns of the two axes, A_d = a_d(g_d)  ([m_d][p_d]; vg_whitened_columns with one length per dimension)
-static int vg_raster_factors(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* A1, double* A2, hipStream_t st) {
+int vg_raster_factors(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* A1, double* A2, hipStream_t st) {
     VgDim &d1 = c->d[0], &d2 = c->d[1];
     VgFactorJob fj[2] = {VgFactorJob{g1, d1.grid, A1, nullptr, nullptr, nullptr, (int)p1, d1.m, d1.kind, d1.basis, 0, 0.0, c->desc.flags},
                          VgFactorJob{g2, d2.grid, A2, nullptr, nullptr, nullptr, (int)p2, d2.m, d2.kind, d2.basis, 1, 0.0, c->desc.flags}};
@@ -137,7 +137,7 @@ static int vg_raster_factors(vggp_ctx* c, const double* g1, long p1, const doubl
 }
 
 // full-grid state: vggp_posterior's preamble (accurate state or thin read-out, compact q1 x q2 weights, W_d = Q_d^T L0_d^-1), once per axis
-static int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, double* var, hipStream_t st) {
+int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, double* var, hipStream_t st) {
     const long m1 = c->desc.m1, m2 = c->desc.m2;
     const bool thin_ro = vg_thin_readout(c);
     int rc = thin_ro ? VGGP_OK : vg_accurate_state(c, st);
@@ -179,7 +179,7 @@ static int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* 
 
 // M-space states (dense masked / scattered, iterative masked, iterative scattered): mean = (s1 s2 / v) U1^T A0 U2 with the state's own
 // m1 x m2 coefficients A0 = mat(a0) and whitened axis factors U_d = L0_d^-1 A_d
-static int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st) {
+int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st) {
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
     const long m1 = w.m1, m2 = w.m2;
     int rc = vg_ensure_misc(c, (size_t)(2 * m1 * p1 + 2 * m2 * p2 + m1 * p2) * sizeof(double));

@@ -9,7 +9,11 @@
 // it, in whatever order and layout.  Index spaces of a sampling call (s = global sample number):
 //     stream 0  E  idx = s M + i1 m2 + i2
 //     stream 1  F  idx = s n1 n2 + j n1 + i on a grid (the layout of Y and W),  idx = s N + k on scattered points
-// Specification: tests/qv_sample_spec.py.
+// and of a raster-sampling call (raster_sample.hip; p1 x p2 raster):
+//     stream 2  G  idx = s p1 p2 + a p2 + b
+//     stream 3  H  idx = s m1 p2 + i p2 + b
+//     stream 4     idx = s p1 p2 + a p2 + b: the observation noise the host layer adds for posterior_predictive_grid().sample()
+// Specification: tests/qv_sample_spec.py, tests/raster_sample_spec.py.
 #include "ctx.h"
 
 __device__ __forceinline__ double vgq_normal(unsigned long long seed, unsigned stream_id, unsigned long long idx) {
@@ -94,6 +98,25 @@ __global__ void vgq_out_kernel(const double* Y, const double* mean, const double
     out[(long)c * m1 * m2 + cell] = mean[cell] + sc * Y[idx];
 }
 
+// raster samples (raster_sample.hip): E[a][c][b] (rows [m1][nbc][w]) = eps[c][a][b] or element (s0 + c) m1 w + a w + b of `stream_id`
+__global__ void vgq_rows_noise_kernel(double* E, const double* eps, unsigned long long seed, unsigned stream_id, unsigned long long s0, int m1,
+                                      int nbc, long w, int cn) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)m1 * nbc * w) return;
+    const long b = idx % w, a = idx / (w * nbc);
+    const int c = (int)((idx / w) % nbc);
+    const unsigned long long n = (unsigned long long)m1 * (unsigned long long)w, cell = (unsigned long long)a * w + b;
+    E[idx] = c >= cn ? 0.0 : (eps ? eps[c * n + cell] : vgq_normal(seed, stream_id, (s0 + c) * n + cell));
+}
+__global__ void vgq_scale_root_kernel(double* x, long n, const double* theta) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] *= sqrt(theta[2] * theta[3]);
+}
+__global__ void vgq_nugget_kernel(double* A, long p, double eta) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < p) A[i * p + i] += eta;
+}
+
 #define VGQ_LAUNCH1D(kern, n, st, ...) hipLaunchKernelGGL(kern, dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, st, __VA_ARGS__)
 
 hipError_t vg_normal_fill_launch(unsigned long long seed, unsigned stream_id, unsigned long long first, long n, double* out, hipStream_t st) {
@@ -122,6 +145,19 @@ hipError_t vg_sample_root_scale_launch(double* X, const double* invD, int m1, in
 hipError_t vg_sample_out_launch(const double* Y, const double* mean, const double* theta, int e1, int e2, int m1, int nbc, int m2, int cn,
                                 double* out, hipStream_t st) {
     VGQ_LAUNCH1D(vgq_out_kernel, (long)m1 * nbc * m2, st, Y, mean, theta, e1, e2, m1, nbc, m2, cn, out);
+    return hipGetLastError();
+}
+hipError_t vg_sample_rows_noise_launch(double* E, const double* eps, unsigned long long seed, unsigned stream_id, unsigned long long s0, int m1,
+                                       int nbc, long w, int cn, hipStream_t st) {
+    VGQ_LAUNCH1D(vgq_rows_noise_kernel, (long)m1 * nbc * w, st, E, eps, seed, stream_id, s0, m1, nbc, w, cn);
+    return hipGetLastError();
+}
+hipError_t vg_sample_scale_root_launch(double* x, long n, const double* theta, hipStream_t st) {
+    VGQ_LAUNCH1D(vgq_scale_root_kernel, n, st, x, n, theta);
+    return hipGetLastError();
+}
+hipError_t vg_sample_nugget_launch(double* A, long p, double eta, hipStream_t st) {
+    VGQ_LAUNCH1D(vgq_nugget_kernel, p, st, A, p, eta);
     return hipGetLastError();
 }
 

@@ -610,6 +610,79 @@ class Engine:
                                             _stream(self.device)))
         return mean, var
 
+    # -- joint samples of posterior(x*) on a raster (include/vggp.h: vggp_posterior_raster_sample*; no p1 p2 x p1 p2 matrix) ------
+    def _raster_sample_args(self, g1, g2, n_samples, eps_u, eps_obs, obs_shape, eps_g, eps_h):
+        a1 = torch.as_tensor(g1).to(self.device, torch.float64).reshape(-1).contiguous()
+        a2 = torch.as_tensor(g2).to(self.device, torch.float64).reshape(-1).contiguous()
+        p1, p2, S = a1.numel(), a2.numel(), int(n_samples)
+        if eps_u is not None and tuple(eps_u.shape) != (S, self.m1, self.m2):
+            raise ValueError(f"eps_u must be [n_samples={S}, m1={self.m1}, m2={self.m2}], got {tuple(eps_u.shape)}")
+        if eps_obs is not None and tuple(eps_obs.shape) != (S,) + obs_shape:
+            raise ValueError(f"eps_obs must be {(S,) + obs_shape}, got {tuple(eps_obs.shape)}")
+        if eps_g is not None and tuple(eps_g.shape) != (S, p1, p2):
+            raise ValueError(f"eps_g must be [n_samples={S}, p1={p1}, p2={p2}], got {tuple(eps_g.shape)}")
+        if eps_h is not None and tuple(eps_h.shape) != (S, self.m1, p2):
+            raise ValueError(f"eps_h must be [n_samples={S}, m1={self.m1}, p2={p2}], got {tuple(eps_h.shape)}")
+        return a1, a2, p1, p2, S, torch.empty(max(S, 0), p1, p2, dtype=torch.float64, device=self.device)
+
+    def posterior_raster_sample(self, g1, g2, n_samples: int, seed: int = 0, first: int = 0, eps_u: Optional[torch.Tensor] = None,
+                                eps_g: Optional[torch.Tensor] = None, eps_h: Optional[torch.Tensor] = None):
+        """n_samples joint samples of posterior(x*) on the raster g1 x g2 after elbo_step (full grid) -> ([n_samples, p1, p2], info).
+        eps_u [n_samples, m1, m2], eps_g [n_samples, p1, p2], eps_h [n_samples, m1, p2]: the caller's standard normals, all or none;
+        none: generated on the device, sample s = first + local of `seed` (sharing E_s with qv_sample).  info['jitter']: the levels
+        the roots took on top of the 1e-8 nugget."""
+        a1, a2, p1, p2, S, out = self._raster_sample_args(g1, g2, n_samples, eps_u, None, (), eps_g, eps_h)
+        info = Info()
+        check(self.lib.vggp_posterior_raster_sample(self._h, _ptr(a1), p1, _ptr(a2), p2, S, int(seed) & (2**64 - 1), int(first), _ptr(eps_u),
+                                                    _ptr(eps_g), _ptr(eps_h), _ptr(out) if S > 0 else None, C.byref(info),
+                                                    _stream(self.device)))
+        return out, self._info(info)
+
+    def posterior_raster_sample_masked_iter(self, g1, g2, W: torch.Tensor, n_obs: float, n_samples: int, seed: int = 0, first: int = 0,
+                                            eps_u: Optional[torch.Tensor] = None, eps_obs: Optional[torch.Tensor] = None,
+                                            eps_g: Optional[torch.Tensor] = None, eps_h: Optional[torch.Tensor] = None, tol: float = 1e-10,
+                                            max_iter: int = 100, block: int = 0):
+        """As posterior_raster_sample after elbo_step_masked_iter (W, n_obs: the step's); eps_obs [n_samples, n2, n1]; one block PCG
+        solve per block of samples (info['rounds'][0] = most PCG iterations, info['sweeps'][0] = block solves)."""
+        self._check_Y(W)
+        a1, a2, p1, p2, S, out = self._raster_sample_args(g1, g2, n_samples, eps_u, eps_obs, (self.n2, self.n1), eps_g, eps_h)
+        info = Info()
+        check(self.lib.vggp_posterior_raster_sample_masked_iter(self._h, _ptr(a1), p1, _ptr(a2), p2, _ptr(W), float(n_obs), S,
+                                                                int(seed) & (2**64 - 1), int(first), _ptr(eps_u), _ptr(eps_obs), _ptr(eps_g),
+                                                                _ptr(eps_h), float(tol), int(max_iter), int(block),
+                                                                _ptr(out) if S > 0 else None, C.byref(info), _stream(self.device)))
+        return out, self._info(info)
+
+    def posterior_raster_sample_scattered_iter(self, g1, g2, n_samples: int, seed: int = 0, first: int = 0,
+                                               eps_u: Optional[torch.Tensor] = None, eps_obs: Optional[torch.Tensor] = None,
+                                               eps_g: Optional[torch.Tensor] = None, eps_h: Optional[torch.Tensor] = None,
+                                               tol: float = 1e-10, max_iter: int = 100, block: int = 0):
+        """As posterior_raster_sample_masked_iter after elbo_step_scattered_iter; eps_obs [n_samples, N]."""
+        a1, a2, p1, p2, S, out = self._raster_sample_args(g1, g2, n_samples, eps_u, eps_obs, (self.n1,), eps_g, eps_h)
+        info = Info()
+        check(self.lib.vggp_posterior_raster_sample_scattered_iter(self._h, _ptr(a1), p1, _ptr(a2), p2, S, int(seed) & (2**64 - 1), int(first),
+                                                                   _ptr(eps_u), _ptr(eps_obs), _ptr(eps_g), _ptr(eps_h), float(tol),
+                                                                   int(max_iter), int(block), _ptr(out) if S > 0 else None,
+                                                                   C.byref(info), _stream(self.device)))
+        return out, self._info(info)
+
+    def raster_sample_contract(self, B1: torch.Tensor, Wt: torch.Tensor, C1: torch.Tensor, Tt: torch.Tensor, c: float = 1.0,
+                               mean: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The raster samplers' kernel on its own (vggp_raster_sample_contract): B1 [q, P1], Wt [S, q, P2], C1 [P1, P1] lower triangular
+        (nothing above its diagonal is read), Tt [S, P1, P2], mean [P1, P2] or None -> out [S, P1, P2] = mean + B1^T Wt[s] + c C1 Tt[s]."""
+        q, P1 = B1.shape
+        S, P2 = Wt.shape[0], Wt.shape[2]
+        if tuple(Wt.shape) != (S, q, P2) or tuple(C1.shape) != (P1, P1) or tuple(Tt.shape) != (S, P1, P2) or \
+                (mean is not None and tuple(mean.shape) != (P1, P2)):
+            raise ValueError("raster_sample_contract: B1 [q, P1], Wt [S, q, P2], C1 [P1, P1], Tt [S, P1, P2], mean [P1, P2]")
+        if out is None:
+            out = torch.empty(S, P1, P2, dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (S, P1, P2):
+            raise ValueError("raster_sample_contract: out must be [S, P1, P2]")
+        check(self.lib.vggp_raster_sample_contract(self._h, _ptr(B1), _ptr(Wt), _ptr(C1), _ptr(Tt), S, q, P1, P2, float(c), _ptr(mean),
+                                                   _ptr(out), _stream(self.device)))
+        return out
+
     # -- exact GP (dense N x N, N <= 16384; a workspace of its own beside the planned model) --------------
     def exact_plan(self, kind1: str, kind2: str, x1, x2) -> None:
         """Exact GP on the N points (x1[k], x2[k]) with kernel_1 * kernel_2 of the given kinds (vggp_exact_plan).  Independent of

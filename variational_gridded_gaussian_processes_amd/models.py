@@ -106,7 +106,9 @@ class MultivariateNormal:
     both iterative solvers (engine side, no M x M matrix) and on the dense masked / scattered states up to M = 4096 (from
     `.covariance_matrix`); this is also the q_u() of the Gridded* classes, the same distribution.  Not attached (sample raises
     NotImplementedError): the gridded q_v() of the Gridded* classes (v != u: a joint residual Kvv - Kvu Kuu^-1 Kuv is needed),
-    posterior(x*), paired inducing points, the 1-D classes, the exact GP, multi-rank contexts."""
+    the point-wise posterior(x*), paired inducing points, the 1-D classes, the exact GP, multi-rank contexts.  posterior_grid() and
+    posterior_predictive_grid() carry a sampler of the whole map on full grids and on both iterative solvers (not on the dense masked /
+    scattered states, not for B1 hats)."""
 
     def __init__(self, mean: torch.Tensor, variance, cov_fn=None, sample_fn=None):
         self.mean = mean
@@ -124,8 +126,9 @@ class MultivariateNormal:
         if self._sample_fn is None:
             raise NotImplementedError("joint samples are not available for this distribution: q_v() of the KroneckerStructure models "
                                       "(full grid, solver='iterative', scattered_solver='iterative', dense states up to M = 4096) "
-                                      "carries a sampler; the gridded q_v() of the Gridded* classes, posterior(x*), paired inducing "
-                                      "points, the 1-D classes and the exact GP do not")
+                                      "and posterior_grid() on full grids and the iterative solvers carry a sampler; the gridded q_v() "
+                                      "of the Gridded* classes, the point-wise posterior(x*), paired inducing points, the 1-D classes "
+                                      "and the exact GP do not")
         shape = torch.Size(sample_shape)
         n = int(np.prod(shape)) if len(shape) else 1
         if n < 1:
@@ -430,7 +433,8 @@ class KroneckerStructure(torch.nn.Module):
         (Engine.qv_sample), on the iterative solvers by one block PCG solve per 64 samples (Engine.qv_sample_masked_iter /
         qv_sample_scattered_iter; no solve runs before sample() is called, last_readout_info holds its PCG counts), on the dense masked /
         scattered states from covariance_matrix up to M = 4096.  Out of scope (sample raises NotImplementedError): the gridded q_v() of
-        the Gridded* classes (v != u), posterior(x*), paired inducing points, the 1-D classes, the exact GP; multi-rank engines refuse."""
+        the Gridded* classes (v != u), the point-wise posterior(x*) (posterior_grid() samples maps), paired inducing points, the 1-D
+        classes, the exact GP; multi-rank engines refuse."""
         self._refresh()
         if self._siter and self.scattered_variances:         # the mean now, the variance of all M cells on first use (as below)
             def svar():
@@ -540,7 +544,11 @@ class KroneckerStructure(torch.nn.Module):
         reference's notebooks), flat index a * P2 + b.  Mean and variance come from Engine.posterior_raster, O(P1 P2 m) instead of
         O(P1 P2 m^2); there is no dense covariance (`.covariance_matrix` raises).  On a grid with holes, on scattered points and on the
         iterative solvers the raster entry gives the mean; the variance then comes from that state's point-wise route (posterior()), on
-        the first use of `.variance`."""
+        the first use of `.variance`.
+        `.sample(torch.Size([S]), seed=None)` draws JOINT samples [S, P1 P2] of the map on full grids and on both iterative solvers
+        (Engine.posterior_raster_sample*: per-axis Cholesky roots of the prior residual, P_d <= 8192, no P1 P2 x P1 P2 matrix; a fixed
+        nugget of 1e-8 at unit outputscale).  It raises NotImplementedError on the dense masked / scattered states (build the model with
+        solver='iterative' resp. scattered_solver='iterative') and for B1 hat features (indefinite residual)."""
         self._refresh()
         a1 = torch.as_tensor(x1_star, dtype=torch.float64).reshape(-1)
         a2 = torch.as_tensor(x2_star, dtype=torch.float64).reshape(-1)
@@ -551,21 +559,65 @@ class KroneckerStructure(torch.nn.Module):
         def no_cov():
             raise NotImplementedError("posterior_grid has no dense covariance (a raster of P1 P2 points); use .variance, or posterior() "
                                       "on a few points for its .covariance_matrix")
+        sampler = self._raster_sampler(a1, a2)
         if not (self._masked or self._scattered):
             mean, var = self._engine.posterior_raster(a1, a2)
-            return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(), cov_fn=no_cov)
+            return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(), cov_fn=no_cov, sample_fn=sampler)
         mean, _ = self._engine.posterior_raster(a1, a2, want_var=False)
 
         def var():                       # (posterior() refreshes the state itself; means-only scattered models raise here as there)
             return self.posterior(torch.cartesian_prod(a1, a2)).variance
-        return MultivariateNormal(mean.reshape(-1).cpu(), var, cov_fn=no_cov)
+        return MultivariateNormal(mean.reshape(-1).cpu(), var, cov_fn=no_cov, sample_fn=sampler)
+
+    def _raster_sampler(self, a1: torch.Tensor, a2: torch.Tensor, predictive: bool = False):
+        """posterior_grid().sample on a full grid and on the iterative solvers: Engine.posterior_raster_sample* (n, seed, first) ->
+        [n, P1 P2] on the host, flat index a P2 + b; sample s of a seed shares its coefficient noise with sample s of q_v().  No root and
+        no solve happens before sample() is called; the iterative solvers leave their PCG counts in last_readout_info.  predictive:
+        plus sqrt(noise) times the engine's stream 4 (idx = s P1 P2 + a P2 + b).  The states that have no raster sampler get a function
+        that raises NotImplementedError with the way out."""
+        name = type(self).__name__
+        if self._basis()[0] == "b1":
+            def refuse(n, seed, first):
+                raise NotImplementedError(f"{name}: joint samples of posterior_grid are not available for B1 hat features: the prior "
+                                          "residual k - q of that basis is indefinite, so the raster covariance has no Kronecker root")
+            return refuse
+        if (self._masked or self._scattered) and not (self._iter or self._siter):      # the dense M-space states
+            which = "scattered_solver='iterative'" if self._scattered else "solver='iterative'"
+
+            def refuse(n, seed, first):
+                raise NotImplementedError(f"{name}: joint samples of posterior_grid need the whitened coefficient draw of the iterative "
+                                          f"state; build the model with {which}")
+            return refuse
+        P = a1.numel() * a2.numel()
+
+        def fn(n, seed, first):
+            self._refresh()              # the engine may have been re-planned by another model since
+            eng = self._engine
+            if self._siter:
+                out, self.last_readout_info = eng.posterior_raster_sample_scattered_iter(a1, a2, n, seed, first, tol=self.tol,
+                                                                                         max_iter=self.max_iter)
+            elif self._iter:
+                out, self.last_readout_info = eng.posterior_raster_sample_masked_iter(a1, a2, self._W, self._nobs, n, seed, first,
+                                                                                      tol=self.tol, max_iter=self.max_iter)
+            else:
+                out, _ = eng.posterior_raster_sample(a1, a2, n, seed, first)
+            out = out.reshape(n, P)
+            if predictive:
+                noise = self.likelihood.noise.detach().to(torch.float64).reshape(()).item()
+                out = out + noise ** 0.5 * eng.normal_fill(seed, 4, first * P, n * P).reshape(n, P)
+            return out.cpu()
+        return fn
 
     def posterior_predictive_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor) -> MultivariateNormal:
-        """posterior_grid with the likelihood's noise variance added (kronecker_structure.py:232-247 on a raster)."""
+        """posterior_grid with the likelihood's noise variance added (kronecker_structure.py:232-247 on a raster).  `.sample()` draws
+        the samples posterior_grid().sample() draws for the seed, plus independent observation noise."""
         p = self.posterior_grid(x1_star, x2_star)
         noise = self.likelihood.noise.detach().to(torch.float64)
         variance = p._variance
-        return MultivariateNormal(p.mean, (lambda: p.variance + noise) if callable(variance) else variance + noise, cov_fn=p._cov_fn)
+        a1 = torch.as_tensor(x1_star, dtype=torch.float64).reshape(-1)
+        a2 = torch.as_tensor(x2_star, dtype=torch.float64).reshape(-1)
+        return MultivariateNormal(p.mean, (lambda: p.variance + noise) if callable(variance) else variance + noise, cov_fn=p._cov_fn,
+                                  sample_fn=self._raster_sampler(a1, a2, predictive=True))
 
     # -- dense views kept for small sizes / debugging (the hot path never forms them) ------------------------------
     def _factor(self, d: int, x: torch.Tensor):
