@@ -462,7 +462,8 @@ int vggp_posterior(vggp_ctx* ctx, const double* xs1, const double* xs2, int64_t 
  *                                       mean = (s1 s2 / sigma^2) U1^T A0 U2 from the state's m1 x m2 coefficients, U_d = L0_d^-1 A_d(g_d);
  *                                       var must be NULL (VGGP_EINVAL before anything is launched: those variances t^T Sigma~^-1 t are no
  *                                       Kronecker sums -- vggp_posterior_masked, vggp_posterior_masked_iter,
- *                                       vggp_posterior_var_scattered_iter give them point by point)
+ *                                       vggp_posterior_var_scattered_iter give them point by point; after the two DENSE steps
+ *                                       vggp_posterior_raster_var_masked below gives mean and variance on the raster)
  * var = NULL: the mean only, on every state.  1 <= p_d <= 2^20; output indices are 64-bit.  Workspace (the context's lazy scratch):
  * 2 m1 p1 + (2 m2 + 2 m1) p2 + m1^2 + m2^2 doubles after a full-grid step (the last two: W_d = Q_d^T L0_d^-1), 2 m1 p1 + (2 m2 + m1) p2
  * after the other steps; nothing of size p1 p2.  VGGP_ESTATE without a finished step (the rules of the state's point-wise
@@ -480,6 +481,38 @@ int vggp_posterior_raster(vggp_ctx* ctx, const double* g1, int64_t p1, const dou
  * may then be NULL) skips the second product.  1 <= q, P1, P2 <= 2^20.  The context need not be planned. */
 int vggp_raster_contract(vggp_ctx* ctx, const double* T1, const double* U, const double* Uv, int64_t q, int64_t P1, int64_t P2,
                          double c0, double c1, double* mean, double* var, void* stream);
+
+/* Mean AND variance on the raster after a successful vggp_elbo_step_masked or vggp_elbo_step_scattered -- the dense M-space states,
+ * where vggp_posterior_raster gives the mean only.  Arguments as vggp_posterior_raster (g1 DEVICE [p1], g2 DEVICE [p2]; mean, var
+ * DEVICE [p1][p2], flat index a p2 + b, both required).  The mean is vggp_posterior_raster's (the same launches, the same bits).  The
+ * variance var = s1 s2 (1 - |t|^2 + t^T Sinv t) is no Kronecker sum -- Sinv = Sigma~^-1 is a dense M x M matrix -- but every raster
+ * column is rank one, t_ab = u1_a (x) u2_b with u_d = L0_d^-1 a_d(g_d), so the quadratic form separates one axis at a time
+ * (vggp_kron_quadform below, n_d = squared column norms of U_d, kd = 1, scale = s1 s2 read from theta on the device):
+ * 2 p1 M^2 + 2 p1 p2 m2^2 flops instead of the 2 p1 p2 M^2 of vggp_posterior_masked at the p1 p2 points, to which it agrees to rounding
+ * (the same form summed in another order; tested at 1e-6 relative, measured: DESIGN.md).  The chunk's intermediate sits in the step's
+ * M x M scratch where vggp_posterior_masked keeps its T; Sinv, a0 and everything a later read-out or step reads is left untouched: the
+ * point-wise read-outs return the same bits before and after, and a call between two steps changes no bit of the second step (tested).
+ * Workspace otherwise: vggp_posterior_raster's 2 m1 p1 + (2 m2 + m1) p2 doubles of the context's lazy scratch.
+ * VGGP_ESTATE unless the LAST finished step on the context is a dense masked / scattered one (not after vggp_plan alone, a full-grid
+ * step or an iterative step: those have no Sinv).  VGGP_EINVAL before anything is launched on paired contexts, multi-rank contexts,
+ * NULL arguments, p_d outside [1, 2^20]. */
+int vggp_posterior_raster_var_masked(vggp_ctx* ctx, const double* g1, int64_t p1, const double* g2, int64_t p2, double* mean, double* var,
+                                     void* stream);
+/* Its contraction as a building block, exported for tests, on caller-supplied DEVICE arrays: S [M][M] (M = m1 m2 <= 16384, flat index
+ * (i m2 + j) M + k m2 + l; it need NOT be symmetric), U1 [m1][P1], U2 [m2][P2], n1 [P1], n2 [P2] (both or neither), out [P1][P2]:
+ *     out[a][b] = scale (kd - n1[a] n2[b] + sum_{i,j,k,l} U1[i][a] U2[j][b] S[(i m2 + j) M + k m2 + l] U1[k][a] U2[l][b])
+ * n1 = n2 = NULL and kd = 0, scale = 1 give the bare quadratic form (u1_a (x) u2_b)^T S (u1_a (x) u2_b).  Two launches of ONE fp64-MFMA
+ * kernel (64 x 64 output tiles) per chunk of the P1 axis,
+ *     Gt[(j,l)][a] = sum_{(i,k)} S((i,k), (j,l)) U1[i][a] U1[k][a]           (m2^2 x chunk, K = m1^2; S read through the index view, no copy)
+ *     out[a][b]    = scale (kd - n1[a] n2[b] + sum_{(j,l)} Gt[(j,l)][a] U2[j][b] U2[l][b])                      (chunk x P2, K = m2^2)
+ * whose second operand, the Khatri-Rao self-product V[p][c] V[q][c], is formed from two coalesced loads and one multiply while the
+ * fragments are staged and never stored.  Edges (K no multiple of 4 or 16, rows / columns no multiple of 64, view tiles that straddle
+ * a j boundary) are handled in the kernel: nothing is padded or copied.  No split-K and no atomics: one wave sums each element in
+ * ascending k, so results are bitwise repeatable.
+ * Chunk rule: the P1 axis is processed in chunks of chunk = min(P1, m1^2) columns (the last one may be shorter), so that Gt -- m2^2 x
+ * chunk doubles of the context's lazy scratch -- never passes M^2 doubles.  1 <= P1, P2 <= 2^20.  The context need not be planned. */
+int vggp_kron_quadform(vggp_ctx* ctx, const double* S, int64_t m1, int64_t m2, const double* U1, int64_t P1, const double* U2, int64_t P2,
+                       const double* n1, const double* n2, double kd, double scale, double* out, void* stream);
 
 /* Joint (correlated) samples of posterior(x*) on a raster: n_samples realisations of f on the p1 x p2 cartesian grid of the axes g1, g2
  * (DEVICE [p1], [p2]), what `.sample()` gives on the MultivariateNormal the reference's posterior() returns for X* = cartesian_prod(g1, g2)

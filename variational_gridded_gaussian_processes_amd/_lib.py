@@ -89,6 +89,8 @@ SYMBOLS = {
     "vggp_posterior": (_I, [_P, _P, _P, _I64, _P, _P, _P]),
     "vggp_posterior_raster": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
     "vggp_raster_contract": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _D, _D, _P, _P, _P]),
+    "vggp_kron_quadform": (_I, [_P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _D, _D, _P, _P]),
+    "vggp_posterior_raster_var_masked": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
     "vggp_posterior_raster_sample": (_I, [_P, _P, _I64, _P, _I64, _I64, C.c_uint64, _I64, _P, _P, _P, _P, C.POINTER(Info), _P]),
     "vggp_posterior_raster_sample_masked_iter": (_I, [_P, _P, _I64, _P, _I64, _P, _D, _I64, C.c_uint64, _I64, _P, _P, _P, _P, _D, _I, _I, _P,
                                                       C.POINTER(Info), _P]),

@@ -119,7 +119,9 @@ int vgi_sample_coeffs(vggp_ctx* c, VgReadout& r, const char* fn, bool scattered,
 // ---- raster.hip: the raster mean of the last step (full-grid state: mean and, with var, variance), axis factor columns A_d = a_d(g_d) ----
 int vg_raster_factors(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* A1, double* A2, hipStream_t st);
 int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, double* var, hipStream_t st);
-int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st);
+struct VgRasterAxes { double *A1, *U1, *A2, *U2; };     // [m_d][p_d] each, in the context's scratch: factor columns, U_d = L0_d^-1 A_d
+int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st,
+                     VgRasterAxes* ax = nullptr);
 // ---- iter_step.hip ---------------------------------------------------------------------------------------------------
 __global__ void vgi_transpose_kernel(const double* W, long n1, long n2, double* Wt);
 __global__ void vgi_mul_kernel(const double* a, const double* b, long n, double* out);

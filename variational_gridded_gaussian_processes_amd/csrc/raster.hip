@@ -178,8 +178,8 @@ int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* g2, lon
 }
 
 // M-space states (dense masked / scattered, iterative masked, iterative scattered): mean = (s1 s2 / v) U1^T A0 U2 with the state's own
-// m1 x m2 coefficients A0 = mat(a0) and whitened axis factors U_d = L0_d^-1 A_d
-int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st) {
+// m1 x m2 coefficients A0 = mat(a0) and whitened axis factors U_d = L0_d^-1 A_d  (ax: where those sit in the scratch afterwards)
+int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st, VgRasterAxes* ax) {
     VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
     const long m1 = w.m1, m2 = w.m2;
     int rc = vg_ensure_misc(c, (size_t)(2 * m1 * p1 + 2 * m2 * p2 + m1 * p2) * sizeof(double));
@@ -190,6 +190,7 @@ int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, l
     double* A2 = p; p += m2 * p2;
     double* U2 = p; p += m2 * p2;
     double* V = p;
+    if (ax) *ax = VgRasterAxes{A1, U1, A2, U2};
     VgDim &d1 = c->d[0], &d2 = c->d[1];
     if ((rc = vg_raster_factors(c, g1, p1, g2, p2, A1, A2, st))) return rc;
     VgGemmBatch g;

@@ -581,7 +581,8 @@ class Engine:
     def posterior_raster(self, g1: torch.Tensor, g2: torch.Tensor, want_var: bool = True):
         """posterior(x*) on the cartesian grid of two coordinate axes (vggp_posterior_raster): g1 [p1], g2 [p2] -> (mean [p1, p2],
         var [p1, p2] or None), element (a, b) at the point (g1[a], g2[b]).  Reads the last finished step, whichever kind; the masked,
-        scattered and iterative states give the mean only (want_var=True raises there: use their point-wise read-outs)."""
+        scattered and iterative states give the mean only (want_var=True raises there: use their point-wise read-outs, or
+        posterior_raster_var_masked after the dense masked / scattered steps)."""
         a1 = torch.as_tensor(g1).to(self.device, torch.float64).reshape(-1).contiguous()
         a2 = torch.as_tensor(g2).to(self.device, torch.float64).reshape(-1).contiguous()
         p1, p2 = a1.numel(), a2.numel()
@@ -609,6 +610,37 @@ class Engine:
         check(self.lib.vggp_raster_contract(self._h, _ptr(T1), _ptr(U), _ptr(Uv), q, P1, P2, float(c0), float(c1), _ptr(mean), _ptr(var),
                                             _stream(self.device)))
         return mean, var
+
+    def posterior_raster_var_masked(self, g1: torch.Tensor, g2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Mean and variance of posterior(x*) on the raster g1 x g2 after elbo_step_masked / elbo_step_scattered
+        (vggp_posterior_raster_var_masked) -> (mean [p1, p2], var [p1, p2]).  The mean is posterior_raster's, bit for bit; the variance
+        is the separable contraction against the state's dense Sinv (kron_quadform), not the point-wise route."""
+        a1 = torch.as_tensor(g1).to(self.device, torch.float64).reshape(-1).contiguous()
+        a2 = torch.as_tensor(g2).to(self.device, torch.float64).reshape(-1).contiguous()
+        p1, p2 = a1.numel(), a2.numel()
+        mean = torch.empty(p1, p2, dtype=torch.float64, device=self.device)
+        var = torch.empty_like(mean)
+        check(self.lib.vggp_posterior_raster_var_masked(self._h, _ptr(a1), p1, _ptr(a2), p2, _ptr(mean), _ptr(var), _stream(self.device)))
+        return mean, var
+
+    def kron_quadform(self, S: torch.Tensor, U1: torch.Tensor, U2: torch.Tensor, n1: Optional[torch.Tensor] = None,
+                      n2: Optional[torch.Tensor] = None, kd: float = 0.0, scale: float = 1.0,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The raster variance's contraction on its own (vggp_kron_quadform): S [M, M] (M = m1 m2, any matrix), U1 [m1, P1], U2 [m2, P2],
+        n1 [P1], n2 [P2] (both or neither) -> out [P1, P2] = scale (kd - n1[a] n2[b] + (u1_a (x) u2_b)^T S (u1_a (x) u2_b)).  Operands
+        and `out` must be contiguous float64 GPU tensors (TypeError otherwise: the kernel receives their pointers)."""
+        m1, P1 = U1.shape
+        m2, P2 = U2.shape
+        if tuple(S.shape) != (m1 * m2, m1 * m2) or (n1 is None) != (n2 is None) or \
+                (n1 is not None and (tuple(n1.shape) != (P1,) or tuple(n2.shape) != (P2,))):
+            raise ValueError("kron_quadform: S [m1 m2, m1 m2], U1 [m1, P1], U2 [m2, P2], n1 [P1] and n2 [P2] (both or neither)")
+        if out is None:
+            out = torch.empty(P1, P2, dtype=torch.float64, device=self.device)
+        elif tuple(out.shape) != (P1, P2):
+            raise ValueError("kron_quadform: out must be [P1, P2]")
+        check(self.lib.vggp_kron_quadform(self._h, _ptr(S), m1, m2, _ptr(U1), P1, _ptr(U2), P2, _ptr(n1), _ptr(n2), float(kd), float(scale),
+                                          _ptr(out), _stream(self.device)))
+        return out
 
     # -- joint samples of posterior(x*) on a raster (include/vggp.h: vggp_posterior_raster_sample*; no p1 p2 x p1 p2 matrix) ------
     def _raster_sample_args(self, g1, g2, n_samples, eps_u, eps_obs, obs_shape, eps_g, eps_h):

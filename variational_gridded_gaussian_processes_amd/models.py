@@ -539,12 +539,15 @@ class KroneckerStructure(torch.nn.Module):
         return MultivariateNormal(p.mean, p.variance + noise,
                                   cov_fn=lambda: p.covariance_matrix + noise * torch.eye(p.mean.shape[0], dtype=p.variance.dtype))
 
-    def posterior_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor) -> MultivariateNormal:
+    def posterior_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor, raster_variance: bool = False) -> MultivariateNormal:
         """posterior(torch.cartesian_prod(x1_star, x2_star)) for a map: the raster of two coordinate axes (the meshgrid cells of the
         reference's notebooks), flat index a * P2 + b.  Mean and variance come from Engine.posterior_raster, O(P1 P2 m) instead of
         O(P1 P2 m^2); there is no dense covariance (`.covariance_matrix` raises).  On a grid with holes, on scattered points and on the
         iterative solvers the raster entry gives the mean; the variance then comes from that state's point-wise route (posterior()), on
-        the first use of `.variance`.
+        the first use of `.variance`.  raster_variance=True on a dense masked / scattered state takes `.variance` from
+        Engine.posterior_raster_var_masked instead (the separable contraction against the state's Sinv: O(P1 M^2 + P1 P2 m2^2), not
+        O(P1 P2 M^2); equal to the point-wise route to rounding, not bit for bit), lazily as well; it changes nothing on a full grid
+        (the raster variance is what is returned there) and raises NotImplementedError on the iterative solvers, which keep no Sinv.
         `.sample(torch.Size([S]), seed=None)` draws JOINT samples [S, P1 P2] of the map on full grids and on both iterative solvers
         (Engine.posterior_raster_sample*: per-axis Cholesky roots of the prior residual, P_d <= 8192, no P1 P2 x P1 P2 matrix; a fixed
         nugget of 1e-8 at unit outputscale).  It raises NotImplementedError on the dense masked / scattered states (build the model with
@@ -563,9 +566,15 @@ class KroneckerStructure(torch.nn.Module):
         if not (self._masked or self._scattered):
             mean, var = self._engine.posterior_raster(a1, a2)
             return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(), cov_fn=no_cov, sample_fn=sampler)
+        if raster_variance and (self._iter or self._siter):
+            raise NotImplementedError(f"{type(self).__name__}: raster_variance=True needs the dense Sinv of the masked / scattered step; "
+                                      f"the iterative solvers keep none -- use posterior(torch.cartesian_prod(x1_star, x2_star)).variance")
         mean, _ = self._engine.posterior_raster(a1, a2, want_var=False)
 
         def var():                       # (posterior() refreshes the state itself; means-only scattered models raise here as there)
+            if raster_variance:
+                self._refresh()          # the engine may have been re-planned by another model since
+                return self._engine.posterior_raster_var_masked(a1, a2)[1].reshape(-1).cpu()
             return self.posterior(torch.cartesian_prod(a1, a2)).variance
         return MultivariateNormal(mean.reshape(-1).cpu(), var, cov_fn=no_cov, sample_fn=sampler)
 
@@ -608,10 +617,10 @@ class KroneckerStructure(torch.nn.Module):
             return out.cpu()
         return fn
 
-    def posterior_predictive_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor) -> MultivariateNormal:
+    def posterior_predictive_grid(self, x1_star: torch.Tensor, x2_star: torch.Tensor, raster_variance: bool = False) -> MultivariateNormal:
         """posterior_grid with the likelihood's noise variance added (kronecker_structure.py:232-247 on a raster).  `.sample()` draws
-        the samples posterior_grid().sample() draws for the seed, plus independent observation noise."""
-        p = self.posterior_grid(x1_star, x2_star)
+        the samples posterior_grid().sample() draws for the seed, plus independent observation noise.  raster_variance: as posterior_grid."""
+        p = self.posterior_grid(x1_star, x2_star, raster_variance=raster_variance)
         noise = self.likelihood.noise.detach().to(torch.float64)
         variance = p._variance
         a1 = torch.as_tensor(x1_star, dtype=torch.float64).reshape(-1)
