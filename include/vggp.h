@@ -725,6 +725,58 @@ int vggp_cholesky_inverse(vggp_ctx* ctx, const double* K, int64_t m, double* L, 
 int vggp_eigh(vggp_ctx* ctx, const double* G, int64_t m, double* lam, double* Qt,
               int32_t* sweeps_out, int flags, void* stream);
 
+/* The four single-workgroup kernels of the thin chain (csrc/step.hip chain_thin: the step of numerically rank-deficient Gram matrices,
+ * RBF factors), one job each on caller-supplied DEVICE arrays, exported for tests.  Each entry validates what its launcher validates
+ * (plus NULL pointers) before any memory is touched -- VGGP_EINVAL otherwise --, launches exactly the kernel a step launches for such a
+ * job (no rider), and synchronises the stream before it returns.  None of them changes what a step launches.
+ *
+ * vggp_pivchol   cold range finder (csrc/thin.hip vg_pivchol_kernel): r steps of diagonally pivoted Cholesky of the symmetric G [m][m];
+ *                row i of V [r][m] is the i-th column l_i.  Pivot = largest residual diagonal, ties to the lowest index, a pivot is used
+ *                once; a step whose pivot is not positive writes row i of Omega [r][m] instead.  1 <= r <= min(m, 64), m <= 256.
+ * vggp_rowqr     row orthonormalisation (csrc/eigh.hip vg_rowqr_kernel_t): V1 [r][m] = the rows of Z [r][m] orthonormalised in the given
+ *                order (classical Gram-Schmidt, re-orthogonalised where a pass removed more than half of a row); also copies cp_n doubles
+ *                cp_src -> cp_dst (cp_n = 0: both may be NULL).  1 <= r <= min(m, 64), m <= 256.  m > 128 selects the wide instantiation
+ *                (four elements per lane), cp_n > 0 at m <= 128 the one with the pass-through copy in registers.
+ * vggp_ritz      Rayleigh-Ritz solve of the symmetric matrix whose lower triangle is tril(Hl Hr^T) (Hl, Hr [r][hk] row-major; the
+ *                product is formed by the eigensolver's producer workgroup, csrc/eigh.hip vg_eigh_kernel, factors staged in LDS when
+ *                r <= 48 and hk <= 128), Newton start first (r <= 48) and Jacobi sweeps when it declines.  lam [r] decreasing, row j
+ *                of W [r][r] = Ritz vector j.  counters_out HOST [4] (may be NULL): [0] logged rotation rounds, [1] iterations or sweeps
+ *                | numerical rank << 8 (Ritz values above 1e-14 of the largest), [2] solver status, [3] the producer's final word: bit 27
+ *                set = the Newton start was taken.  err_out HOST (may be NULL): the eigensolver's error bits.  1 <= r <= 64,
+ *                r <= hk <= 256: the envelope of the two chains (the product form exists in the solver's LDS variant only, so the
+ *                launcher's own bound r <= 256 does not hold for it).  VGGP_ENOCONV when [2] or the error bits are set.
+ * vggp_thin_tail the thin m-space stage (csrc/thin.hip vg_thin_tail_kernel): from the Ritz pairs and the r x r sandwiches to the bound, its
+ *                gradient, beta and 1/D on range x range, the subspace-miss check and the packed 128-byte result block.  All arrays
+ *                DEVICE; out [8], beta_out / invd_out [r1][r2] (both or neither), peer_fail, jit[d], status[d] ([2]: Cholesky status,
+ *                eigensolver error bits) and rcounters[d] ([4]) may be NULL; hout [16] doubles (the result block: out[8], jitter[2],
+ *                int32 counters[2][4], int32 status[2], sequence number = theta[5]) may be NULL too.  1 <= r_d <= min(m_d, 32),
+ *                m_d <= 256, ac_nslab >= 1. */
+typedef struct vggp_thin_tail_args {
+    const double* theta;              /* [6]: ell1, ell2, s1, s2, v, sequence number */
+    double n_total, yy;
+    int32_t r1, r2, m1, m2;
+    const double *W1, *W2;            /* [r][r], row j = Ritz vector j */
+    const double *lam1, *lam2;        /* [r] Ritz values, unit scale, decreasing */
+    const double *AM1, *AH1, *AM2, *AH2;   /* [r][r]: V1 Mk0 V1^T, V1 H0 V1^T */
+    const double* AC;                 /* [3][r1][r2]: V1_1 {C, C1, C2} V1_2^T, as the fixed-order sum of ac_nslab slabs ac_slab doubles apart */
+    int32_t ac_nslab;
+    int64_t ac_slab;
+    const double *G1, *H1, *G2, *H2;  /* [m][m]: only the diagonals are read */
+    double* out;
+    double *beta_out, *invd_out;
+    double* hout;
+    const double* peer_fail;
+    const double* jit[2];
+    const int32_t* status[2];
+    const int32_t* rcounters[2];
+} vggp_thin_tail_args;
+int vggp_pivchol(vggp_ctx* ctx, const double* G, const double* Omega, int64_t m, int64_t r, double* V, void* stream);
+int vggp_rowqr(vggp_ctx* ctx, const double* Z, int64_t r, int64_t m, double* V1, const double* cp_src, double* cp_dst, int64_t cp_n,
+               void* stream);
+int vggp_ritz(vggp_ctx* ctx, const double* Hl, const double* Hr, int64_t r, int64_t hk, double* lam, double* W, int32_t* counters_out,
+              int32_t* err_out, void* stream);
+int vggp_thin_tail(vggp_ctx* ctx, const vggp_thin_tail_args* args, void* stream);
+
 /* Strided fp64 MFMA GEMM  C[M][N] = op(A) op(B)  with element (i,k) of op(A) at
  * A[i*sa_m + k*sa_k] and (k,j) of op(B) at B[k*sb_k + j*sb_n]; C row-major, ld = ldc. */
 int vggp_gemm(vggp_ctx* ctx, const double* A, int64_t sa_m, int64_t sa_k,

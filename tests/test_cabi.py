@@ -42,9 +42,11 @@ def test_library_exports_nothing_beyond_the_header(lib):
 
 
 def test_struct_layouts_match_header():
-    from variational_gridded_gaussian_processes_amd._lib import Desc, Info
+    from variational_gridded_gaussian_processes_amd._lib import Desc, Info, ThinTailArgs
     assert C.sizeof(Desc) == 4 * 4 + 5 * 8 + 4 * 8 + 2 * 4
     assert C.sizeof(Info) == 2 * 8 + 6 * 4
+    assert C.sizeof(ThinTailArgs) == 3 * 8 + 4 * 4 + 9 * 8 + 2 * 8 + 4 * 8 + 5 * 8 + 3 * 2 * 8 == 248      # vggp_thin_tail_args
+    assert ThinTailArgs.ac_slab.offset == 120 and ThinTailArgs.rcounters.offset == 232
 
 
 def test_version_and_stage_names(lib):

@@ -1,6 +1,8 @@
 """Thin (range-only) evaluation of the m-space ELBO + gradient for numerically rank-deficient Gram matrices (RBF):
 only the r leading eigenpairs of G_d are used, the null block is treated as exactly zero.  Compares with oracle/kron.py's
-full finish() at the headline configuration."""
+full finish() at the headline configuration.
+(The same formula, for any float dtype and in the kernel's own inputs -- Ritz pairs, r x r sandwiches, diagonals -- is
+tests/thin_chain_spec.py thin_tail(); tests/test_thin_chain_spec.py pins that one to finish() and the GPU tests use it.)"""
 import sys, os, math, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np

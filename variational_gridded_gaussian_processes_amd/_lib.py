@@ -41,6 +41,17 @@ class Info(C.Structure):
                 ("status", C.c_int32), ("polished", C.c_int32)]
 
 
+class ThinTailArgs(C.Structure):      # vggp_thin_tail_args
+    _fields_ = [("theta", C.c_void_p), ("n_total", C.c_double), ("yy", C.c_double),
+                ("r1", C.c_int32), ("r2", C.c_int32), ("m1", C.c_int32), ("m2", C.c_int32),
+                ("W1", C.c_void_p), ("W2", C.c_void_p), ("lam1", C.c_void_p), ("lam2", C.c_void_p),
+                ("AM1", C.c_void_p), ("AH1", C.c_void_p), ("AM2", C.c_void_p), ("AH2", C.c_void_p), ("AC", C.c_void_p),
+                ("ac_nslab", C.c_int32), ("ac_slab", C.c_int64),
+                ("G1", C.c_void_p), ("H1", C.c_void_p), ("G2", C.c_void_p), ("H2", C.c_void_p),
+                ("out", C.c_void_p), ("beta_out", C.c_void_p), ("invd_out", C.c_void_p), ("hout", C.c_void_p),
+                ("peer_fail", C.c_void_p), ("jit", C.c_void_p * 2), ("status", C.c_void_p * 2), ("rcounters", C.c_void_p * 2)]
+
+
 # every symbol include/vggp.h declares: name -> (restype, argtypes)
 _P, _I64, _D, _I = C.c_void_p, C.c_int64, C.c_double, C.c_int
 SYMBOLS = {
@@ -116,6 +127,10 @@ SYMBOLS = {
     "vggp_factor_build": (_I, [_P, _I, _I, _P, _I64, _P, _I64, _D, _I, _P, _P, _P, _P, _P]),
     "vggp_cholesky_inverse": (_I, [_P, _P, _I64, _P, _P, C.POINTER(_D), _P]),
     "vggp_eigh": (_I, [_P, _P, _I64, _P, _P, C.POINTER(C.c_int32), _I, _P]),
+    "vggp_pivchol": (_I, [_P, _P, _P, _I64, _I64, _P, _P]),
+    "vggp_rowqr": (_I, [_P, _P, _I64, _I64, _P, _P, _P, _I64, _P]),
+    "vggp_ritz": (_I, [_P, _P, _P, _I64, _I64, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _P]),
+    "vggp_thin_tail": (_I, [_P, C.POINTER(ThinTailArgs), _P]),
     "vggp_gemm": (_I, [_P, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _P]),
     "vggp_kron_solve": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P]),
     "vggp_trsm": (_I, [_P, _P, _I64, _P, _I64, _P, _I, _P]),

@@ -934,6 +934,99 @@ extern "C" int vggp_eigh(vggp_ctx* c, const double* G, int64_t m, double* lam, d
     return VGGP_OK;
 }
 
+// ---- the thin chain's kernels, one job each (exported for tests: tests/test_gpu_thin_chain_paths.py) ---------------------------------
+extern "C" int vggp_pivchol(vggp_ctx* c, const double* G, const double* Omega, int64_t m, int64_t r, double* V, void* stream) {
+    if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(G && Omega && V, "vggp_pivchol: null argument");
+    VG_REQUIRE(m >= 1 && m <= 256 && r >= 1 && r <= m && r <= 64, "vggp_pivchol: need 1 <= r <= min(m, 64), m <= 256");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const VgPivCholJob j{G, Omega, V, (int)m, (int)r};
+    VG_HIP(vg_pivchol_launch(&j, 1, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+extern "C" int vggp_rowqr(vggp_ctx* c, const double* Z, int64_t r, int64_t m, double* V1, const double* cp_src, double* cp_dst, int64_t cp_n,
+                          void* stream) {
+    if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(Z && V1, "vggp_rowqr: null argument");
+    VG_REQUIRE(r >= 1 && r <= 64 && m >= r && m <= 256, "vggp_rowqr: need 1 <= r <= min(m, 64), m <= 256");
+    VG_REQUIRE(cp_n >= 0 && cp_n < (1L << 31) && (cp_n == 0 || (cp_src && cp_dst)), "vggp_rowqr: bad pass-through copy");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const VgRowQrJob j{Z, V1, (int)r, (int)m, cp_src, cp_dst, (long)cp_n};
+    VG_HIP(vg_rowqr_launch(&j, 1, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
+extern "C" int vggp_ritz(vggp_ctx* c, const double* Hl, const double* Hr, int64_t r, int64_t hk, double* lam, double* W, int32_t* counters_out,
+                         int32_t* err_out, void* stream) {
+    if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(Hl && Hr && lam && W, "vggp_ritz: null argument");
+    VG_REQUIRE(r >= 1 && r <= 64 && hk >= r && hk <= 256, "vggp_ritz: need 1 <= r <= 64, r <= hk <= 256");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    const long m2e = r + (r & 1);                                    // (scratch as vggp_eigh lays it out)
+    const int max_rounds = (int)(VG_EIG_MAXSWEEP * (m2e - 1));
+    const size_t logb = (vg_eigh_log_bytes((int)r) + 15) & ~size_t(15);
+    const size_t need = (size_t)m2e * (m2e + 1) * 8 + logb + (size_t)max_rounds * 4 + 256 + (size_t)m2e * 4 + 64;
+    int rc = vg_ensure_misc(c, need);
+    if (rc) return rc;
+    char* p = (char*)c->misc;
+    double* gwork = (double*)p; p += (size_t)m2e * (m2e + 1) * 8;
+    double2* rotlog = (double2*)p; p += logb;
+    int* roundlog = (int*)p; p += (size_t)max_rounds * 4;
+    p = (char*)(((uintptr_t)p + 63) & ~uintptr_t(63));
+    int* counters = (int*)p;
+    int* perm = counters + 16;
+    VgClearArgs clr;
+    clr.n = 1;
+    clr.ptr[0] = counters; clr.nwords[0] = 8;
+    VG_HIP(vg_clear_launch(&clr, st));
+    const VgEigJob j = vg_make_ritz_job(Hl, Hr, (int)r, (int)hk, lam, W, gwork, rotlog, roundlog, counters, max_rounds, (long)logb, perm,
+                                        counters + 4);
+    VG_HIP(vg_eigh_launch(&j, 1, st));
+    int hc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    VG_HIP(hipMemcpyAsync(hc, counters, sizeof(hc), hipMemcpyDeviceToHost, st));
+    VG_HIP(hipStreamSynchronize(st));
+    if (counters_out) for (int q = 0; q < 4; ++q) counters_out[q] = hc[q];
+    if (err_out) *err_out = hc[4];
+    if (hc[2] || hc[4]) { vg_set_error("vggp_ritz: no convergence"); return VGGP_ENOCONV; }
+    return VGGP_OK;
+}
+
+extern "C" int vggp_thin_tail(vggp_ctx* c, const vggp_thin_tail_args* a, void* stream) {
+    if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }
+    VG_REQUIRE(a, "vggp_thin_tail: null argument block");
+    VG_REQUIRE(a->theta && a->W1 && a->W2 && a->lam1 && a->lam2 && a->AM1 && a->AH1 && a->AM2 && a->AH2 && a->AC && a->G1 && a->H1 && a->G2 &&
+               a->H2, "vggp_thin_tail: null input");
+    VG_REQUIRE(!a->beta_out == !a->invd_out, "vggp_thin_tail: beta_out and invd_out go together");
+    VG_REQUIRE(a->r1 >= 1 && a->r2 >= 1 && a->r1 <= VG_THIN_MAXR && a->r2 <= VG_THIN_MAXR && a->r1 <= a->m1 && a->r2 <= a->m2 && a->m1 <= 256 &&
+               a->m2 <= 256, "vggp_thin_tail: need 1 <= r_d <= min(m_d, 32), m_d <= 256");
+    VG_REQUIRE(a->ac_nslab >= 1 && a->ac_nslab <= 64 && (a->ac_nslab == 1 || a->ac_slab >= 3L * a->r1 * a->r2),
+               "vggp_thin_tail: need 1 <= ac_nslab <= 64 and slabs that do not overlap");
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    static_assert(sizeof(VgHostOut) == 16 * sizeof(double), "vggp_thin_tail_args::hout is 16 doubles");
+    static_assert(sizeof(vggp_thin_tail_args) == 248, "vggp_thin_tail_args layout (_lib.py ThinTailArgs)");
+    VgThinTail tt{};
+    tt.theta = a->theta; tt.n_total = a->n_total; tt.yy = a->yy;
+    tt.r1 = a->r1; tt.r2 = a->r2; tt.m1 = a->m1; tt.m2 = a->m2;
+    tt.W1 = a->W1; tt.W2 = a->W2; tt.lam1 = a->lam1; tt.lam2 = a->lam2;
+    tt.AM1 = a->AM1; tt.AH1 = a->AH1; tt.AM2 = a->AM2; tt.AH2 = a->AH2; tt.AC = a->AC;
+    tt.ac_nslab = a->ac_nslab; tt.ac_slab = (long)a->ac_slab;
+    tt.G1 = a->G1; tt.H1 = a->H1; tt.G2 = a->G2; tt.H2 = a->H2;
+    tt.out = a->out; tt.beta_out = a->beta_out; tt.invd_out = a->invd_out;
+    tt.hout = reinterpret_cast<VgHostOut*>(a->hout);
+    tt.peer_fail = a->peer_fail;
+    for (int k = 0; k < 2; ++k) { tt.jit[k] = a->jit[k]; tt.status[k] = a->status[k]; tt.rcounters[k] = a->rcounters[k]; }
+    VG_HIP(vg_thin_tail_launch(&tt, st));
+    VG_HIP(hipStreamSynchronize(st));
+    return VGGP_OK;
+}
+
 extern "C" int vggp_gemm(vggp_ctx* c, const double* A, int64_t sa_m, int64_t sa_k, const double* B, int64_t sb_k,
                          int64_t sb_n, double* C, int64_t ldc, int64_t M, int64_t N, int64_t K, void* stream) {
     if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }

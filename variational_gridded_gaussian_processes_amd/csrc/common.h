@@ -236,6 +236,15 @@ hipError_t vg_refine_launch(const VgRefineJob* jobs, int njobs, hipStream_t st, 
 size_t vg_eigh_log_bytes(int m);     // log capacity needed for an m x m problem (scalar or block variant)
 hipError_t vg_eigh_launch(const VgEigJob* jobs, int njobs, hipStream_t st, const VgGemmBatch* rider = nullptr);
 hipError_t vg_eigh_setup();
+// Ritz problem of the subspace and thin chains (step.hip) and of vggp_ritz (api.hip): the launch forms H = Hl Hr^T itself (r x hk
+// factors) and solves it from the Newton start; pairs leave sorted by decreasing Ritz value (perm), bit 0 of *err on a replay timeout
+inline VgEigJob vg_make_ritz_job(const double* Hl, const double* Hr, int r, int hk, double* lam, double* W, double* gwork, double2* rotlog,
+                                 int* roundlog, int* counters, int max_rounds, long log_bytes, int* perm, int* err) {
+    VgEigJob j{nullptr, lam, W, nullptr, gwork, rotlog, roundlog, counters, r, max_rounds, log_bytes, 0};
+    j.Hl = Hl; j.Hr = Hr; j.hk = hk;
+    j.perm = perm; j.err = err; j.newton = 1;
+    return j;
+}
 
 // ---- m-space elementwise / reductions (mspace.hip) -----------------------------
 #define VG_ESUBMISS (-100)   // internal status: the subspace start of the eigensolver chain missed part of the range (never returned

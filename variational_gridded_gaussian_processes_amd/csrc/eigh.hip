@@ -1632,9 +1632,12 @@ __device__ __forceinline__ void vg_rowqr_body(const VgRowQrJob& J, double* V) {
 #pragma unroll
         for (int u = 0; u < (CP ? 16 : 1); ++u) { const long i = tid + u * 1024L; cpv[u] = i < J.cp_n ? J.cp_src[i] : 0.0; }
     }
-    for (int i = tid; i < r * m; i += 1024) V[i] = J.Z[i];
+    // (the last block of an r that is no multiple of 4 is filled up with zero rows: c = 0, |x|^2 = 0, no second pass asked for, scale 0
+    //  -- they cost nothing the real rows see and are not copied out; vg_rowqr_launch sizes the LDS for them)
+    const int rpad = (r + 3) & ~3;
+    for (int i = tid; i < rpad * m; i += 1024) V[i] = i < r * m ? J.Z[i] : 0.0;
     __syncthreads();
-    // Block Gram-Schmidt, 4 rows at a time (r is a multiple of 4): the block is projected off all finished rows twice
+    // Block Gram-Schmidt, 4 rows at a time (r padded to a multiple of 4): the block is projected off all finished rows twice
     // (4 k0 dot products per pass, 16 lanes each, one barrier; 4 x EW threads subtract), then wave 0 alone orthonormalises the
     // four rows among themselves in registers (NE elements per lane, wave reductions, no workgroup barrier).
     // "Twice is enough", but only where it is needed (Kahan / Parlett): a projection is repeated when it removed more than
@@ -1769,7 +1772,7 @@ hipError_t vg_rowqr_launch(const VgRowQrJob* jobs, int njobs, hipStream_t st, co
     for (int j = 0; j < njobs; ++j) {
         a.job[j] = jobs[j];
         if (jobs[j].r < 1 || jobs[j].r > 64 || jobs[j].m < jobs[j].r || jobs[j].m > 256) return hipErrorInvalidValue;
-        const size_t need = (size_t)jobs[j].r * jobs[j].m * sizeof(double);
+        const size_t need = (size_t)((jobs[j].r + 3) & ~3) * jobs[j].m * sizeof(double);      // whole blocks of four rows
         if (need > lds) lds = need;
     }
     // (separate kernels, not branches: a kernel's register allocation is the maximum over its paths -- the pass-through copy holds

@@ -443,11 +443,8 @@ int VgFinish::start_times_G(const double* S1, int rows1, const double* S2, int r
 
 // Ritz problem of the subspace and thin chains: the launch forms H = T V1^T itself (Hl, Hr) and solves it from the Newton start
 static VgEigJob vg_ritz_job(VgDim& d) {
-    VgEigJob j{nullptr, d.lam_s, d.Ws, nullptr, d.gwork2, d.rotlog2, d.roundlog2, d.counters2, d.sub_r, d.max_rounds,
-               (long)vg_eigh_log_bytes(d.m), 0};
-    j.Hl = d.Zs; j.Hr = d.V1s; j.hk = d.m;
-    j.perm = d.perm2; j.err = d.status + 1; j.newton = 1;
-    return j;
+    return vg_make_ritz_job(d.Zs, d.V1s, d.sub_r, d.m, d.lam_s, d.Ws, d.gwork2, d.rotlog2, d.roundlog2, d.counters2, d.max_rounds,
+                            (long)vg_eigh_log_bytes(d.m), d.perm2, d.status + 1);
 }
 
 // multi-rank step: the word behind the payload travelled through the all-reduce; non-zero = some rank failed its partials

@@ -884,6 +884,37 @@ class Engine:
                                  _lib.FLAG_BLOCK_JACOBI if block else 0, _stream(self.device)))
         return lam, Qt, sw.value
 
+    # the thin chain's kernels, one job each (include/vggp.h; tests/test_gpu_thin_chain_paths.py)
+    def pivchol(self, G: torch.Tensor, Omega: torch.Tensor) -> torch.Tensor:
+        """-> V[r,m]: r = Omega.shape[0] steps of diagonally pivoted Cholesky of G[m,m], the columns as rows."""
+        r, m = Omega.shape
+        V = torch.empty(r, m, dtype=torch.float64, device=self.device)
+        check(self.lib.vggp_pivchol(self._h, _ptr(G), _ptr(Omega), m, r, _ptr(V), _stream(self.device)))
+        return V
+
+    def rowqr(self, Z: torch.Tensor, cp_src: torch.Tensor = None) -> torch.Tensor:
+        """-> V1[r,m], the rows of Z orthonormalised in their order (and the pass-through copy of cp_src, when given)."""
+        r, m = Z.shape
+        V1 = torch.empty_like(Z)
+        cp_dst = torch.empty_like(cp_src) if cp_src is not None else None
+        check(self.lib.vggp_rowqr(self._h, _ptr(Z), r, m, _ptr(V1), _ptr(cp_src) if cp_src is not None else None,
+                                  _ptr(cp_dst) if cp_src is not None else None, cp_src.numel() if cp_src is not None else 0,
+                                  _stream(self.device)))
+        return V1 if cp_src is None else (V1, cp_dst)
+
+    def ritz(self, Hl: torch.Tensor, Hr: torch.Tensor):
+        """-> lam[r] (decreasing), W[r,r] (row j = Ritz vector j), counters[4], err of the matrix whose lower triangle is tril(Hl Hr^T)."""
+        r, hk = Hl.shape
+        lam = torch.empty(r, dtype=torch.float64, device=self.device)
+        W = torch.empty(r, r, dtype=torch.float64, device=self.device)
+        cnt, err = (C.c_int32 * 4)(), C.c_int32()
+        check(self.lib.vggp_ritz(self._h, _ptr(Hl), _ptr(Hr), r, hk, _ptr(lam), _ptr(W), cnt, C.byref(err), _stream(self.device)))
+        return lam, W, list(cnt), err.value
+
+    def thin_tail(self, args: "_lib.ThinTailArgs") -> None:
+        """The thin m-space stage on the device arrays named by `args` (see vggp_thin_tail_args)."""
+        check(self.lib.vggp_thin_tail(self._h, C.byref(args), _stream(self.device)))
+
     def gemm(self, A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
         """C = A @ B for 2-D float64 GPU tensors with arbitrary strides (no copies are made)."""
         M, K = A.shape
