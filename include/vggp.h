@@ -413,6 +413,37 @@ int vggp_qv_sample_masked_iter(vggp_ctx* ctx, const double* W, double n_obs, int
                                vggp_info* info, void* stream);
 int vggp_qv_sample_scattered_iter(vggp_ctx* ctx, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u,
                                   const double* eps_obs, double tol, int max_iter, int block, double* out, vggp_info* info, void* stream);
+/* The same samples from the DENSE M-space state of the last successful vggp_elbo_step_masked or vggp_elbo_step_scattered (one entry for
+ * both data kinds, as vggp_qv_masked).  The step keeps Xg = L^-1, the inverse of the Cholesky factor of Sigma~ = L L^T, lower triangular,
+ * and the coefficient draw is
+ *     X_s = Xg^T E_s,     Cov(vec X_s) = Xg^T Xg = Sigma~^-1,
+ * one launch of vggp_tri_t_apply's kernel per block of min(64, block, n_samples) samples: no factorisation, no solve, no tolerance and no
+ * M x M temporary, at every M <= 16384.  (A root of Sigma~^-1 other than the symmetric one: the samples have the distribution of
+ * vggp_qv_cov_masked, they are not the numbers a symmetric root gives.)  The mean is vggp_qv_masked's, bit for bit; the tail -- L0_1 X
+ * L0_2^T, the scale, the mean -- is the iterative entries'.  eps_u DEVICE [n_samples][m1][m2] or NULL (stream 0 from (seed, first), the
+ * E_s of every other sampler); there is no eps_obs, W, tol or max_iter; info->rounds* and info->sweeps* are 0 (info may be NULL).  Sample
+ * s of a seed is the same numbers whatever n_samples, block or call asks for it, bit for bit; zero noise returns the mean bit for bit.
+ * Workspace: 4 M nbc + M doubles of the samplers' own scratch (the raster samplers'); the step's state -- Xg, the factor, Sigma~^-1,
+ * a0 -- is only read: the point-wise read-outs return the same bits before and after, and a call between two steps changes no bit of
+ * the second step.  VGGP_ESTATE unless the LAST finished step on the context is a successful dense masked / scattered one (not after
+ * vggp_plan alone, a full-grid step or an iterative step); VGGP_EINVAL before anything is launched or written on paired contexts,
+ * multi-rank contexts, n_samples < 1, first < 0, a NULL out, block > 64. */
+int vggp_qv_sample_masked(vggp_ctx* ctx, int64_t n_samples, uint64_t seed, int64_t first, const double* eps_u, int block, double* out,
+                          vggp_info* info, void* stream);
+/* Its product as a building block, exported for tests, on caller-supplied DEVICE arrays: Xl [M][M] row-major, M = m1 m2 <= 16384, lower
+ * triangular -- NOTHING above its diagonal is read (NaN included); E and out block vectors in the samplers' interleaved layout
+ * [m1][nbc][m2], element (cell u = i1 m2 + i2, column c) at (i1 nbc + c) m2 + i2; 1 <= cn <= nbc <= 64:
+ *     out(u, c) = sum_{k >= u} Xl[k][u] E(k, c)  for c < cn,     out(u, c) = 0  for cn <= c < nbc.
+ * ONE fp64-MFMA kernel: the sample columns are one operand, a 32-column tile of Xl the other (row k of Xl is contiguous along u: the
+ * triangle streams once, in 256-byte runs).  Workgroup b takes column tile b and its mirror nt - 1 - b, so every workgroup streams the
+ * same number of rows (static balance, no work queue); M = 16384 gives 256 workgroups.  Each output element is summed by one wave in
+ * ascending k from the first row of its tile: no split-K, no atomics, bitwise repeatable, and the bits of a column depend neither on
+ * its position in the block nor on cn or nbc.  Edges (M no multiple of 4, 16, 32 or 64, a tile that straddles an i1 boundary of the
+ * layout, cn < nbc < 64, M < nbc, M = 1) are handled in the kernel: nothing is padded or copied.  Indices are 64-bit.  The launch is
+ * asynchronous on `stream`.  VGGP_EINVAL: a NULL argument, sizes outside the ranges above, out == E (the product cannot run in place).
+ * The context need not be planned.  (VGGP_TRI_T_GEMM=1 in the environment routes a call with m1 = 1 through the batch GEMM and its
+ * 128-granular triangular skip instead: the yardstick of tools/bench_dense_sample.py, not a route any sampler takes.) */
+int vggp_tri_t_apply(vggp_ctx* ctx, const double* Xl, int64_t m1, int64_t m2, const double* E, int nbc, int cn, double* out, void* stream);
 
 /* Gradient of the ELBO of the LAST vggp_elbo_step with respect to the inducing-point coordinates of the "points" basis
  * (Matern12SVGP and friends register Z as a trainable Parameter, kronecker_structure.py:303-304, and let autograd differentiate
@@ -556,6 +587,16 @@ int vggp_posterior_raster_sample_scattered_iter(vggp_ctx* ctx, const double* g1,
                                                 uint64_t seed, int64_t first, const double* eps_u, const double* eps_obs, const double* eps_g,
                                                 const double* eps_h, double tol, int max_iter, int block, double* out, vggp_info* info,
                                                 void* stream);
+/* The same map samples from the dense M-space state of the last successful vggp_elbo_step_masked or vggp_elbo_step_scattered: X_s =
+ * Xg^T E_s as vggp_qv_sample_masked draws it (the same launch on the same E_s: sample s of a seed is one joint draw across the two
+ * entries), mu = the mean vggp_posterior_raster returns in this state, then the roots, the nugget, info->jitter1 / jitter2, the block
+ * rule and the kernels of the entries above, unchanged.  No eps_obs, W, tol or max_iter: nothing is solved, info->rounds* and
+ * info->sweeps* are 0.  Workspace: the list above plus 2 nbc m1 m2 doubles (E and X); the step's state is only read (the rules of
+ * vggp_qv_sample_masked).  VGGP_ESTATE unless the LAST finished step is a successful dense masked / scattered one; VGGP_EINVAL before
+ * anything is launched or written: the list of the entries above. */
+int vggp_posterior_raster_sample_masked(vggp_ctx* ctx, const double* g1, int64_t p1, const double* g2, int64_t p2, int64_t n_samples,
+                                        uint64_t seed, int64_t first, const double* eps_u, const double* eps_g, const double* eps_h, int block,
+                                        double* out, vggp_info* info, void* stream);
 /* Their last kernel as a building block, exported for tests, on caller-supplied DEVICE arrays: B1 [q][P1], Wt [S][q][P2], C1 [P1][P1]
  * lower triangular, Tt [S][P1][P2], mean [P1][P2] or NULL, out [S][P1][P2]:
  *     out[s][a][b] = mean[a][b] + sum_i B1[i][a] Wt[s][i][b] + c sum_{a' <= a} C1[a][a'] Tt[s][a'][b]

@@ -93,6 +93,8 @@ SYMBOLS = {
     "vggp_qv_sample": (_I, [_P, _I64, C.c_uint64, _I64, _P, _P, _P]),
     "vggp_qv_sample_masked_iter": (_I, [_P, _P, _D, _I64, C.c_uint64, _I64, _P, _P, _D, _I, _I, _P, C.POINTER(Info), _P]),
     "vggp_qv_sample_scattered_iter": (_I, [_P, _I64, C.c_uint64, _I64, _P, _P, _D, _I, _I, _P, C.POINTER(Info), _P]),
+    "vggp_qv_sample_masked": (_I, [_P, _I64, C.c_uint64, _I64, _P, _I, _P, C.POINTER(Info), _P]),
+    "vggp_tri_t_apply": (_I, [_P, _P, _I64, _I64, _P, _I, _I, _P, _P]),
     "vggp_normal_fill": (_I, [_P, C.c_uint64, _I, _I64, _I64, _P, _P]),
     "vggp_zgrad": (_I, [_P, _P, _P, _P, _P]),
     "vggp_zgrad_scattered": (_I, [_P, _P, _P, _P, _P]),
@@ -107,6 +109,7 @@ SYMBOLS = {
                                                       C.POINTER(Info), _P]),
     "vggp_posterior_raster_sample_scattered_iter": (_I, [_P, _P, _I64, _P, _I64, _I64, C.c_uint64, _I64, _P, _P, _P, _P, _D, _I, _I, _P,
                                                          C.POINTER(Info), _P]),
+    "vggp_posterior_raster_sample_masked": (_I, [_P, _P, _I64, _P, _I64, _I64, C.c_uint64, _I64, _P, _P, _P, _I, _P, C.POINTER(Info), _P]),
     "vggp_raster_sample_contract": (_I, [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _D, _P, _P, _P]),
     "vggp_readout": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I, _P]),
     "vggp_readout_masked": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _I, _P]),

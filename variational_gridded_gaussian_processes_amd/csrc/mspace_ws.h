@@ -3,6 +3,7 @@
 //   masked_readout.hip  the dense read-outs
 //   iter_step.hip       VgIter machinery (block PCG, basis policy, traces), the two iterative steps
 //   iter_readout.hip    the iterative read-outs: point-wise, joint samples, gridded
+//   dense_sample.hip    joint samples on the dense states: the triangular product X = Xg^T E, vggp_qv_sample_masked
 // A kernel or helper named here is defined in the file its comment names; everything else is static to its file.
 #pragma once
 #include "arena.h"
@@ -122,6 +123,12 @@ int vg_raster_full(vggp_ctx* c, const double* g1, long p1, const double* g2, lon
 struct VgRasterAxes { double *A1, *U1, *A2, *U2; };     // [m_d][p_d] each, in the context's scratch: factor columns, U_d = L0_d^-1 A_d
 int vg_raster_mspace(vggp_ctx* c, const double* g1, long p1, const double* g2, long p2, double* mean, hipStream_t st,
                      VgRasterAxes* ax = nullptr);
+// ---- raster_sample.hip: the samplers' own scratch (c->rs_mem), grown to `bytes` when it is smaller ----
+int vg_rs_reserve(vggp_ctx* c, const char* fn, size_t bytes, int nbc);
+// ---- dense_sample.hip: the coefficient draw of the dense states, out = Xl^T E on block vectors [m1][nbc][m2] (Xl [M][M] lower
+// triangular, cn live columns, the others written as zeros; out != E), and what both of their samplers check before they launch ----
+hipError_t vg_tri_t_apply_launch(const double* Xl, long m1, long m2, const double* E, int nbc, int cn, double* out, hipStream_t st);
+int vg_dense_sample_enter(vggp_ctx* c, const char* fn, int64_t n_samples, int64_t first, const void* out, int block, vggp_info* info);
 // ---- iter_step.hip ---------------------------------------------------------------------------------------------------
 __global__ void vgi_transpose_kernel(const double* W, long n1, long n2, double* Wt);
 __global__ void vgi_mul_kernel(const double* a, const double* b, long n, double* out);

@@ -212,23 +212,31 @@ static int vg_rs_check(const vggp_ctx* c, const char* fn, const double* g1, int6
     return VGGP_OK;
 }
 
-// workspace, the axis factors and the three roots.  xab: doubles of the full-grid coefficient draw's two block vectors (0 on the
-// iterative states, whose draw lives in the read-outs' workspace)
-static int vg_rs_setup(vggp_ctx* c, const char* fn, VgRasterSample& z, const double* g1, const double* g2, long xab, vggp_info* info, hipStream_t st) {
-    const long m1 = z.m1, m2 = z.m2, p1 = z.p1, p2 = z.p2, pm = std::max(p1, p2);
-    const size_t need = (size_t)(p1 * p2 + 2 * m1 * p1 + 2 * m2 * p2 + 2 * p1 * p1 + 3 * p2 * p2 + pm * pm + 2 * m1 * z.nbc * p2 +
-                                 (long)z.nbc * p1 * p2 + 2 * xab) * sizeof(double);
+// the samplers' own scratch (also vggp_qv_sample_masked's, dense_sample.hip): kept while it is large enough, replaced when it is not
+int vg_rs_reserve(vggp_ctx* c, const char* fn, size_t need, int nbc) {
     if (c->rs_bytes < need) {
         if (c->rs_mem) { VG_HIP(hipFree(c->rs_mem)); c->rs_mem = nullptr; c->rs_bytes = 0; }
         if (hipMalloc(&c->rs_mem, need) != hipSuccess) {
             (void)hipGetLastError();
             c->rs_mem = nullptr;
-            vg_set_error("%s: the workspace of a block of %d samples needs %.1f GiB of device memory (a smaller block needs less)", fn, z.nbc,
+            vg_set_error("%s: the workspace of a block of %d samples needs %.1f GiB of device memory (a smaller block needs less)", fn, nbc,
                          (double)need / (1024.0 * 1024.0 * 1024.0));
             return VGGP_ENOMEM;
         }
         c->rs_bytes = need;
     }
+    return VGGP_OK;
+}
+
+// workspace, the axis factors and the three roots.  xab: doubles of each of the coefficient draw's two block vectors where the draw
+// lives here (full grid: eigenbasis coefficients and draw; dense states: E and X = Xg^T E; 0 on the iterative states, whose draw lives
+// in the read-outs' workspace)
+static int vg_rs_setup(vggp_ctx* c, const char* fn, VgRasterSample& z, const double* g1, const double* g2, long xab, vggp_info* info, hipStream_t st) {
+    const long m1 = z.m1, m2 = z.m2, p1 = z.p1, p2 = z.p2, pm = std::max(p1, p2);
+    const size_t need = (size_t)(p1 * p2 + 2 * m1 * p1 + 2 * m2 * p2 + 2 * p1 * p1 + 3 * p2 * p2 + pm * pm + 2 * m1 * z.nbc * p2 +
+                                 (long)z.nbc * p1 * p2 + 2 * xab) * sizeof(double);
+    int rrc = vg_rs_reserve(c, fn, need, z.nbc);
+    if (rrc) return rrc;
     double* p = (double*)c->rs_mem;
     z.mean = p; p += p1 * p2;
     z.A1 = p; p += m1 * p1;
@@ -379,6 +387,40 @@ static int vg_rs_iter_run(vggp_ctx* c, const char* fn, bool scattered, const dou
             return rc;
     }
     VGI_WAIT(c, st);
+    return VGGP_OK;
+}
+
+// the dense masked / scattered states: the coefficient draw is X = Xg^T E, one launch of dense_sample.hip's triangular product on the
+// inverse factor the step keeps (no solve: info->rounds* and sweeps* stay 0); E and X are the setup's two block vectors
+extern "C" int vggp_posterior_raster_sample_masked(vggp_ctx* c, const double* g1, int64_t p1, const double* g2, int64_t p2, int64_t n_samples,
+                                                   uint64_t seed, int64_t first, const double* eps_u, const double* eps_g, const double* eps_h,
+                                                   int block, double* out, vggp_info* info, void* stream) {
+    static const char* fn = "vggp_posterior_raster_sample_masked";
+    VG_NOT_PAIRED(c, fn);
+    if (!c || !c->planned) { vg_set_error("%s: context not planned", fn); return VGGP_ESTATE; }
+    VG_REQUIRE(!vgi_multi(c), "%s: joint samples run on single-rank contexts only (this context is multi-rank)", fn);
+    int rc = vg_rs_check(c, fn, g1, p1, g2, p2, eps_u, eps_g, eps_h, nullptr, false);
+    if (rc) return rc;
+    if ((rc = vg_dense_sample_enter(c, fn, n_samples, first, out, block, info))) return rc;
+    VG_ENTER_DEVICE(c->device);
+    hipStream_t st = stream ? (hipStream_t)stream : c->own_stream;
+    VgMasked& w = *reinterpret_cast<VgMasked*>(c->masked);
+    VgRasterSample z{};
+    z.m1 = w.m1; z.m2 = w.m2; z.p1 = p1; z.p2 = p2;
+    z.nbc = vg_rs_block(block, n_samples, p1, p2);
+    const long M = w.M;
+    if ((rc = vg_rs_setup(c, fn, z, g1, g2, M * z.nbc, info, st))) return rc;
+    if ((rc = vg_raster_mspace(c, g1, p1, g2, p2, z.mean, st))) return rc;
+    for (int64_t off = 0; off < n_samples; off += z.nbc) {
+        const int cn = (int)std::min<int64_t>(z.nbc, n_samples - off);
+        const unsigned long long s0 = (unsigned long long)(first + off);
+        VG_HIP(vg_sample_block_noise_launch(z.Xa, eps_u ? eps_u + off * M : nullptr, seed, s0, (int)z.m1, z.nbc, (int)z.m2, cn, st));
+        VG_HIP(vg_tri_t_apply_launch(w.Xg, z.m1, z.m2, z.Xa, z.nbc, cn, z.Xb, st));
+        if ((rc = vg_rs_block_out(c, z, z.Xb, eps_g ? eps_g + off * p1 * p2 : nullptr, eps_h ? eps_h + off * z.m1 * p2 : nullptr, seed, s0, cn,
+                                  out + off * p1 * p2, st)))
+            return rc;
+    }
+    VG_HIP(hipStreamSynchronize(st));
     return VGGP_OK;
 }
 

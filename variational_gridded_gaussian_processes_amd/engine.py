@@ -508,6 +508,31 @@ class Engine:
                                                      _stream(self.device)))
         return out, self._info(info)
 
+    def qv_sample_masked(self, n_samples: int, seed: int = 0, first: int = 0, eps_u: Optional[torch.Tensor] = None, block: int = 0):
+        """Joint samples of q(v) after elbo_step_masked / elbo_step_scattered (the dense states) -> ([n_samples, m1, m2], info): the
+        coefficient draw X = Xg^T E from the inverse factor the step keeps, one launch per `block` <= 64 samples, nothing solved
+        (info['rounds'] and info['sweeps'] are 0).  eps_u [n_samples, m1, m2] or None (generated from seed / first as qv_sample)."""
+        S, out = self._sample_noise(n_samples, eps_u, None, ())
+        info = Info()
+        check(self.lib.vggp_qv_sample_masked(self._h, S, int(seed) & (2**64 - 1), int(first), _ptr(eps_u), int(block),
+                                             _ptr(out) if S > 0 else None, C.byref(info), _stream(self.device)))
+        return out, self._info(info)
+
+    def tri_t_apply(self, Xl: torch.Tensor, E: torch.Tensor, cn: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The dense samplers' product on its own (vggp_tri_t_apply): Xl [M, M] lower triangular (nothing above its diagonal is read),
+        E [m1, nbc, m2] with M = m1 m2 -> out [m1, nbc, m2], out(u, c) = sum_{k >= u} Xl[k, u] E(k, c) for c < cn (None: nbc), zeros
+        for c >= cn.  Asynchronous on torch's current stream."""
+        m1, nbc, m2 = E.shape
+        if tuple(Xl.shape) != (m1 * m2, m1 * m2):
+            raise ValueError("tri_t_apply: Xl [m1 m2, m1 m2], E [m1, nbc, m2]")
+        if out is None:
+            out = torch.empty_like(E)
+        elif tuple(out.shape) != tuple(E.shape):
+            raise ValueError("tri_t_apply: out must be [m1, nbc, m2]")
+        check(self.lib.vggp_tri_t_apply(self._h, _ptr(Xl), m1, m2, _ptr(E), nbc, nbc if cn is None else int(cn), _ptr(out),
+                                        _stream(self.device)))
+        return out
+
     def readout(self, C1: torch.Tensor, C2: torch.Tensor, kd1: torch.Tensor, kd2: torch.Tensor, literal: bool = True,
                 masked: bool = False):
         """Gridded read-out q(v) of B0 cell features from the inducing posterior of the last step (include/vggp.h):
@@ -696,6 +721,17 @@ class Engine:
                                                                    _ptr(eps_u), _ptr(eps_obs), _ptr(eps_g), _ptr(eps_h), float(tol),
                                                                    int(max_iter), int(block), _ptr(out) if S > 0 else None,
                                                                    C.byref(info), _stream(self.device)))
+        return out, self._info(info)
+
+    def posterior_raster_sample_masked(self, g1, g2, n_samples: int, seed: int = 0, first: int = 0, eps_u: Optional[torch.Tensor] = None,
+                                       eps_g: Optional[torch.Tensor] = None, eps_h: Optional[torch.Tensor] = None, block: int = 0):
+        """As posterior_raster_sample after elbo_step_masked / elbo_step_scattered (the dense states): the coefficient draw of
+        qv_sample_masked (sample s of a seed shares its E_s), nothing solved."""
+        a1, a2, p1, p2, S, out = self._raster_sample_args(g1, g2, n_samples, eps_u, None, (), eps_g, eps_h)
+        info = Info()
+        check(self.lib.vggp_posterior_raster_sample_masked(self._h, _ptr(a1), p1, _ptr(a2), p2, S, int(seed) & (2**64 - 1), int(first),
+                                                           _ptr(eps_u), _ptr(eps_g), _ptr(eps_h), int(block),
+                                                           _ptr(out) if S > 0 else None, C.byref(info), _stream(self.device)))
         return out, self._info(info)
 
     def raster_sample_contract(self, B1: torch.Tensor, Wt: torch.Tensor, C1: torch.Tensor, Tt: torch.Tensor, c: float = 1.0,

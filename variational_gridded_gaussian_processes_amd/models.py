@@ -108,7 +108,8 @@ class MultivariateNormal:
     NotImplementedError): the gridded q_v() of the Gridded* classes (v != u: a joint residual Kvv - Kvu Kuu^-1 Kuv is needed),
     the point-wise posterior(x*), paired inducing points, the 1-D classes, the exact GP, multi-rank contexts.  posterior_grid() and
     posterior_predictive_grid() carry a sampler of the whole map on full grids and on both iterative solvers (not on the dense masked /
-    scattered states, not for B1 hats)."""
+    scattered states, not for B1 hats).  A model built with dense_samples=True draws both on the engine on the dense states as well,
+    at any M the dense solver takes (KroneckerStructure.__init__)."""
 
     def __init__(self, mean: torch.Tensor, variance, cov_fn=None, sample_fn=None):
         self.mean = mean
@@ -236,7 +237,8 @@ class KroneckerStructure(torch.nn.Module):
     kind = "matern12"
 
     def __init__(self, X: torch.Tensor, y: torch.Tensor, engine: Optional[Engine] = None, warm_start: bool = True,
-                 solver: str = "auto", scattered_solver: str = "auto", scattered_variances: bool = False):
+                 solver: str = "auto", scattered_solver: str = "auto", scattered_variances: bool = False,
+                 dense_samples: bool = False):
         """solver: how a grid with holes is solved.  "dense": the M x M solver (M = m1 m2 <= 16384); "iterative": PCG without any
         M x M matrix (Engine.elbo_step_masked_iter and its read-outs; also accepted on a full grid, which it treats as a mask of
         ones); "auto": iterative only for a grid with holes whose M exceeds the dense solver's limit, dense everywhere else.
@@ -251,7 +253,13 @@ class KroneckerStructure(torch.nn.Module):
         scattered_variances: on the iterative scattered solver, give q_v(), q_u(), posterior() and posterior_predictive() their
         point-wise variances (Engine.qv_var_scattered_iter / posterior_var_scattered_iter: ceil(columns / 64) block PCG solves; the
         all-cell variance of q_v() is computed on first use).  False keeps the means-only distributions, whose .variance raises;
-        q_v_at(cells) gives the variance of a few cells either way.  No effect on the other solvers."""
+        q_v_at(cells) gives the variance of a few cells either way.  No effect on the other solvers.
+        dense_samples: on the dense masked / scattered states (without paired inducing points), draw joint samples on the engine
+        from the inverse factor the step keeps (Engine.qv_sample_masked / posterior_raster_sample_masked: X = Xg^T E, one launch per
+        64 samples, nothing solved and no M x M temporary): q_v().sample works at every M <= 16384, posterior_grid().sample and
+        posterior_predictive_grid().sample draw maps, and sample s of a seed is one joint draw across q_v() and the map, as on the
+        other solvers.  False (the default) keeps q_v().sample on the symmetric root of covariance_matrix (M <= 4096; other numbers,
+        the same distribution) and the raster samplers refusing.  No effect on full grids and on the iterative solvers."""
         super().__init__()
         if solver not in ("auto", "dense", "iterative"):
             raise ValueError(f"solver must be 'auto', 'dense' or 'iterative', got {solver!r}")
@@ -260,6 +268,7 @@ class KroneckerStructure(torch.nn.Module):
         self.solver = solver
         self.scattered_solver = scattered_solver
         self.scattered_variances = bool(scattered_variances)
+        self.dense_samples = bool(dense_samples)
         self.last_readout_info = None    # PCG counts of the last variance read-out on an iterative solver
         self._siter = False              # the iterative scattered step applies (decided at plan time)
         self.n_probes, self.tol, self.max_iter = 16, 1e-10, 100      # of the iterative solver (the engine's defaults)
@@ -432,7 +441,8 @@ class KroneckerStructure(torch.nn.Module):
         `.sample(torch.Size([S]), seed=None)` draws joint samples [S, M]: on a full grid from the step's Kronecker eigenbasis
         (Engine.qv_sample), on the iterative solvers by one block PCG solve per 64 samples (Engine.qv_sample_masked_iter /
         qv_sample_scattered_iter; no solve runs before sample() is called, last_readout_info holds its PCG counts), on the dense masked /
-        scattered states from covariance_matrix up to M = 4096.  Out of scope (sample raises NotImplementedError): the gridded q_v() of
+        scattered states from covariance_matrix up to M = 4096 -- or, with dense_samples=True, from the step's inverse factor at any M
+        (Engine.qv_sample_masked).  Out of scope (sample raises NotImplementedError): the gridded q_v() of
         the Gridded* classes (v != u), the point-wise posterior(x*) (posterior_grid() samples maps), paired inducing points, the 1-D
         classes, the exact GP; multi-rank engines refuse."""
         self._refresh()
@@ -459,7 +469,7 @@ class KroneckerStructure(torch.nn.Module):
             qv = MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
                                     cov_fn=lambda: self._engine.qv_cov_masked().cpu())
             if not self._engine.paired:  # (paired inducing points: no sampler)
-                qv._sample_fn = self._dense_sampler(qv)
+                qv._sample_fn = self._dense_engine_sampler() if self.dense_samples else self._dense_sampler(qv)
             return qv
         mean, var = self._engine.qv()
         return MultivariateNormal(mean.reshape(-1).cpu(), var.reshape(-1).cpu(),
@@ -493,6 +503,15 @@ class KroneckerStructure(torch.nn.Module):
                                           f"build the model with {which}, whose sampler needs no M x M matrix")
             eps = self._engine.normal_fill(seed, 0, first * M, n * M).reshape(n, M).cpu()
             return qv.mean[None, :] + eps @ _symmetric_root(qv.covariance_matrix)
+        return fn
+
+    def _dense_engine_sampler(self):
+        """q_v().sample on the dense masked / scattered states with dense_samples=True: Engine.qv_sample_masked (n, seed, first) ->
+        [n, M] on the host, any M the dense solver takes; nothing is solved (last_readout_info: zero counts)."""
+        def fn(n, seed, first):
+            self._refresh()              # the engine may have been re-planned by another model since
+            out, self.last_readout_info = self._engine.qv_sample_masked(n, seed, first)
+            return out.reshape(n, -1).cpu()
         return fn
 
     def q_v_at(self, cells) -> MultivariateNormal:
@@ -551,7 +570,8 @@ class KroneckerStructure(torch.nn.Module):
         `.sample(torch.Size([S]), seed=None)` draws JOINT samples [S, P1 P2] of the map on full grids and on both iterative solvers
         (Engine.posterior_raster_sample*: per-axis Cholesky roots of the prior residual, P_d <= 8192, no P1 P2 x P1 P2 matrix; a fixed
         nugget of 1e-8 at unit outputscale).  It raises NotImplementedError on the dense masked / scattered states (build the model with
-        solver='iterative' resp. scattered_solver='iterative') and for B1 hat features (indefinite residual)."""
+        solver='iterative' resp. scattered_solver='iterative', or with dense_samples=True: Engine.posterior_raster_sample_masked) and
+        for B1 hat features (indefinite residual)."""
         self._refresh()
         a1 = torch.as_tensor(x1_star, dtype=torch.float64).reshape(-1)
         a2 = torch.as_tensor(x2_star, dtype=torch.float64).reshape(-1)
@@ -581,8 +601,8 @@ class KroneckerStructure(torch.nn.Module):
     def _raster_sampler(self, a1: torch.Tensor, a2: torch.Tensor, predictive: bool = False):
         """posterior_grid().sample on a full grid and on the iterative solvers: Engine.posterior_raster_sample* (n, seed, first) ->
         [n, P1 P2] on the host, flat index a P2 + b; sample s of a seed shares its coefficient noise with sample s of q_v().  No root and
-        no solve happens before sample() is called; the iterative solvers leave their PCG counts in last_readout_info.  predictive:
-        plus sqrt(noise) times the engine's stream 4 (idx = s P1 P2 + a P2 + b).  The states that have no raster sampler get a function
+        no solve happens before sample() is called; the iterative solvers leave their PCG counts in last_readout_info (the dense states
+        with dense_samples=True: Engine.posterior_raster_sample_masked, zero counts).  predictive: plus sqrt(noise) times the engine's stream 4 (idx = s P1 P2 + a P2 + b).  The states that have no raster sampler get a function
         that raises NotImplementedError with the way out."""
         name = type(self).__name__
         if self._basis()[0] == "b1":
@@ -590,7 +610,8 @@ class KroneckerStructure(torch.nn.Module):
                 raise NotImplementedError(f"{name}: joint samples of posterior_grid are not available for B1 hat features: the prior "
                                           "residual k - q of that basis is indefinite, so the raster covariance has no Kronecker root")
             return refuse
-        if (self._masked or self._scattered) and not (self._iter or self._siter):      # the dense M-space states
+        dense = (self._masked or self._scattered) and not (self._iter or self._siter)      # the dense M-space states
+        if dense and not self.dense_samples:
             which = "scattered_solver='iterative'" if self._scattered else "solver='iterative'"
 
             def refuse(n, seed, first):
@@ -602,7 +623,9 @@ class KroneckerStructure(torch.nn.Module):
         def fn(n, seed, first):
             self._refresh()              # the engine may have been re-planned by another model since
             eng = self._engine
-            if self._siter:
+            if dense:
+                out, self.last_readout_info = eng.posterior_raster_sample_masked(a1, a2, n, seed, first)
+            elif self._siter:
                 out, self.last_readout_info = eng.posterior_raster_sample_scattered_iter(a1, a2, n, seed, first, tol=self.tol,
                                                                                          max_iter=self.max_iter)
             elif self._iter:
