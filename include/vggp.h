@@ -56,7 +56,7 @@ extern "C" {
 
 /* inducing-feature basis of one dimension */
 #define VGGP_BASIS_POINTS 0       /* pairwise k(z, x): Matern12SVGP, kronecker_structure.py:306-338 */
-#define VGGP_BASIS_B0     1       /* B0-spline cell integrals (Matern-1/2 only):
+#define VGGP_BASIS_B0     1       /* B0-spline cell integrals (Matern-1/2 only; the other kernels' cells are VGGP_BASIS_B0K):
                                      kronecker_structure.py:702-790 == gridded_kronecker_structure.py:1286-1374 */
 #define VGGP_BASIS_ONE    2       /* trivial factor K=[1], A=1: turns the engine into the 1-D model,
                                      univariate_structure.py:234-263, :693-717 */
@@ -66,6 +66,11 @@ extern "C" {
 #define VGGP_BASIS_B1     4       /* B1-spline (hat function) features (Matern-1/2 only): Matern12B1SplineASVGP,
                                      kronecker_structure.py:524-660.  grid = knot mesh (m knots).
                                      Kuu_d = (A ell + B / ell + BC) / (2 s_d), Kuf_d = hats(x). */
+#define VGGP_BASIS_B0K    5       /* B0 cells under the dimension's own kernel: the features of VGGP_BASIS_B0 (grid = mesh of m + 1
+                                     equispaced knots, cell k = (g_k, g_k+1], x <= g_0 counts as below; Kuu_d = s_d K0, Kuf_d = s_d A0)
+                                     with K0 = double cell integral and A0 = cell integral of the Matern-1/2, -3/2 or -5/2 profile.
+                                     Matern-1/2 runs the code of VGGP_BASIS_B0 (bit-equal outputs); RBF is refused, and so is
+                                     VGGP_FLAG_B0_F32_KDELTA (the reference has no such model whose rounding could be reproduced). */
 
 /* The reference keeps the B0 mesh and delta as float32 attributes (torch.linspace default
  * dtype; Module.to(float64) does not touch them), so `(k - 1) * delta` in _Kuu_along_dim
@@ -131,8 +136,8 @@ typedef struct vggp_desc {
     int64_t n_total;              /* number of observations over ALL ranks (N)        */
     const double* x1;             /* HOST [n1]  unique coordinates along dim 1        */
     const double* x2;             /* HOST [n2]  local coordinates along dim 2         */
-    const double* grid1;          /* HOST: mesh [m1+1] (B0) or inducing coords [m1]   */
-    const double* grid2;          /* HOST: mesh [m2+1] (B0) or inducing coords [m2]   */
+    const double* grid1;          /* HOST: mesh [m1+1] (B0, B0K) or inducing coords [m1] */
+    const double* grid2;          /* HOST: mesh [m2+1] (B0, B0K) or inducing coords [m2] */
     int32_t warm_start;           /* 1: reuse the previous step's eigenvectors        */
     int32_t flags;                /* VGGP_FLAG_* bit mask                             */
 } vggp_desc;
@@ -725,7 +730,7 @@ int vggp_normal_fill(vggp_ctx* ctx, uint64_t seed, int stream_id, int64_t first_
 
 /* Unit-outputscale factor build for one dimension: A0[m][n], dA0/d ell [m][n],
  * K0[m][m], dK0/d ell [m][m] (any output pointer may be NULL).  x DEVICE [n];
- * grid DEVICE ([m+1] mesh for B0, [m] coords for POINTS).
+ * grid DEVICE ([m+1] mesh for B0 and B0K, [m] coords for POINTS).
  * Replaces _Kuu_along_dim/_Kuf_along_dim (kronecker_structure.py:702-790) and the
  * pairwise kernel_d(Z), kernel(Z, x) evaluations (:318-319, :336-337).
  * Range: every ell > 0 gives finite outputs.  The B0 Kuu is evaluated as ell^2 e^{-(k-1)t} expm1(-t)^2 with
@@ -733,8 +738,11 @@ int vggp_normal_fill(vggp_ctx* ctx, uint64_t seed, int stream_id, int64_t first_
  * neighbour-cell covariance tends to ell^2, cells further apart underflow to 0).  At LARGE ell / delta the B0 closed forms
  * cancel: relative error about eps * ell/delta in A0 and K0 and eps * (ell/delta)^2 in dA0 and dK0 (5e-11 at
  * ell = 320 delta, 7e-7 at ell = 3.2e4 delta; table in DESIGN.md section 5a); with VGGP_FLAG_B0_F32_KDELTA the
- * reference-literal three-exponential Kuu loses a further factor ell/delta.
- * VGGP_EINVAL: ell <= 0, B0 / VFF / B1 with a kind other than Matern-1/2, a NULL grid, a NULL x with A0 or dA0 requested.
+ * reference-literal three-exponential Kuu loses a further factor ell/delta.  The B0K forms of Matern-3/2 and -5/2 (edge-term
+ * differences for A0, E (a0 + k a1 + k^2 a2) with expm1-built mesh constants for K0) are finite for every ell > 0 as well and cancel
+ * more steeply at large ell / delta (their derivatives fall off like (delta/ell)^3): table in DESIGN.md section 5a.
+ * VGGP_EINVAL: ell <= 0, B0 / VFF / B1 with a kind other than Matern-1/2, B0K with RBF or with VGGP_FLAG_B0_F32_KDELTA, a NULL grid,
+ * a NULL x with A0 or dA0 requested.
  * n = 0 is allowed (only K0 / dK0 are written). */
 int vggp_factor_build(vggp_ctx* ctx, int kind, int basis, const double* x, int64_t n,
                       const double* grid, int64_t m, double ell, int flags,

@@ -17,7 +17,7 @@ FLAG_B0_F32_KDELTA = 1
 FLAG_BLOCK_JACOBI = 2
 FLAG_SCATTERED = 4
 FLAG_PAIRED_Z = 8
-BASIS = {"points": 0, "b0": 1, "one": 2, "vff": 3, "b1": 4}
+BASIS = {"points": 0, "b0": 1, "one": 2, "vff": 3, "b1": 4, "b0k": 5}
 
 
 class VggpError(RuntimeError):

@@ -45,14 +45,20 @@ class B0SplineBasis(SplineBasis):
 
     order = 0
 
-    def __init__(self, mesh: torch.Tensor, engine=None):
+    def __init__(self, mesh: torch.Tensor, engine=None, kind: str = "matern12"):
         super().__init__(mesh, engine)
         self.n_basis_functions = int(self.m)
+        self.kind = kind
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         x = torch.as_tensor(x)
         lo, hi = self.mesh[:-1, None], self.mesh[1:, None]
         return torch.logical_and(x[None, :] >= lo, x[None, :] <= hi) * 1
+
+    def cell_integrals(self, x: torch.Tensor, lengthscale: float) -> torch.Tensor:
+        """The unit-outputscale cross-covariance of the cell features with f(x), int_{cell k} kappa(x - t) dt (n_basis x n), of the
+        model's kernel: through VGGP_BASIS_B0 for Matern-1/2 and VGGP_BASIS_B0K for Matern-3/2 / -5/2."""
+        return self._features(self.kind, "b0" if self.kind == "matern12" else "b0k", self.mesh.double().numpy(), x, float(lengthscale))
 
 
 class B1SplineBasis(SplineBasis):

@@ -9,7 +9,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["api.hip", "step.hip", "gemm.hip", "factor_build.hip", "chol.hip", "trsm.hip", "eigh.hip", "mspace.hip", "thin.hip", "masked.hip", "masked_readout.hip", "iter_step.hip", "iter_readout.hip", "kr.hip", "comm.hip", "paired.hip", "exact.hip", "exact_iter.hip", "sample.hip", "raster.hip", "raster_sample.hip", "raster_var.hip", "dense_sample.hip"]
-HEADERS = ["arena.h", "block_pcg.h", "common.h", "ctx.h", "factor_elem.h", "gemm_body.h", "gen_gemm.h", "lanczos_quad.h", "mspace_ws.h", os.path.join("..", "..", "include", "vggp.h")]
+HEADERS = ["arena.h", "block_pcg.h", "common.h", "ctx.h", "factor_elem.h", "factor_kernel_body.h", "gemm_body.h", "gen_gemm.h", "lanczos_quad.h", "mspace_ws.h", os.path.join("..", "..", "include", "vggp.h")]
 LIB = os.path.join(HERE, "libvggp_hip.so")
 
 

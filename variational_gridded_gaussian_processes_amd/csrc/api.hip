@@ -124,7 +124,7 @@ static int pick_split(int tiles, int K, int target) {
 
 // number of doubles in the host/device `grid` array of a dimension
 static long vg_grid_len(int basis, long m) {
-    if (basis == VGGP_BASIS_B0) return m + 1;                 // mesh knots
+    if (basis == VGGP_BASIS_B0 || basis == VGGP_BASIS_B0K) return m + 1;      // mesh knots
     if (basis == VGGP_BASIS_VFF) return 2 + (m - 1) / 2 + 1;  // a, b, omega_0 .. omega_M (m = 2M + 1)
     return m;                                                 // points / B1 knots / trivial
 }
@@ -249,13 +249,15 @@ static void layout(vggp_ctx* c, VgArena& b) {
 
 static int check_dim(int kind, int basis, long n, long m, const char* which) {
     VG_REQUIRE(kind >= 0 && kind <= 3, "vggp_plan: bad kind for %s", which);
-    VG_REQUIRE(basis >= 0 && basis <= 4, "vggp_plan: bad basis for %s", which);
+    VG_REQUIRE(basis >= 0 && basis <= 5, "vggp_plan: bad basis for %s", which);
     VG_REQUIRE(!((basis == VGGP_BASIS_VFF || basis == VGGP_BASIS_B1) && kind != VGGP_KIND_MATERN12),
                "vggp_plan: the VFF and B1 features exist for Matern-1/2 only (%s)", which);
     VG_REQUIRE(!(basis == VGGP_BASIS_VFF && (m < 3 || (m & 1) == 0)), "vggp_plan: VFF needs m = 2M + 1 >= 3 (%s)", which);
     VG_REQUIRE(!(basis == VGGP_BASIS_B1 && m < 2), "vggp_plan: B1 needs at least 2 knots (%s)", which);
     VG_REQUIRE(!(basis == VGGP_BASIS_B0 && kind != VGGP_KIND_MATERN12),
                "vggp_plan: the B0 basis exists for Matern-1/2 only (%s)", which);
+    VG_REQUIRE(!(basis == VGGP_BASIS_B0K && kind == VGGP_KIND_RBF),
+               "vggp_plan: the B0K cells exist for the Matern-1/2, -3/2 and -5/2 kernels (%s)", which);
     VG_REQUIRE(n >= 1, "vggp_plan: %s has no observations", which);
     VG_REQUIRE(m >= 1 && m <= 256, "vggp_plan: m=%ld for %s outside [1, 256]", m, which);
     VG_REQUIRE(!(basis == VGGP_BASIS_ONE && m != 1), "vggp_plan: BASIS_ONE needs m=1 (%s)", which);
@@ -286,6 +288,8 @@ extern "C" int vggp_plan(vggp_ctx* c, const vggp_desc* desc) {
     if (c->is_paired || c->paired) { VG_HIP(hipDeviceSynchronize()); vg_paired_free(c); c->is_paired = false; }
     if ((rc = check_dim(desc->kind1, desc->basis1, desc->n1, desc->m1, "dimension 1"))) return rc;
     if ((rc = check_dim(desc->kind2, desc->basis2, desc->n2, desc->m2, "dimension 2"))) return rc;
+    VG_REQUIRE(!((desc->basis1 == VGGP_BASIS_B0K || desc->basis2 == VGGP_BASIS_B0K) && (desc->flags & VGGP_FLAG_B0_F32_KDELTA)),
+               "vggp_plan: VGGP_FLAG_B0_F32_KDELTA does not go with VGGP_BASIS_B0K");
     VG_REQUIRE(desc->x1 && desc->x2, "vggp_plan: null coordinate arrays");
     VG_REQUIRE((desc->basis1 == VGGP_BASIS_ONE || desc->grid1) && (desc->basis2 == VGGP_BASIS_ONE || desc->grid2),
                "vggp_plan: null grid arrays");
@@ -819,10 +823,12 @@ extern "C" int vggp_readout(vggp_ctx* c, const double* C1, int64_t mv1, const do
 extern "C" int vggp_factor_build(vggp_ctx* c, int kind, int basis, const double* x, int64_t n, const double* grid,
                                  int64_t m, double ell, int flags, double* A0, double* dA0, double* K0, double* dK0, void* stream) {
     if (!c) { vg_set_error("null context"); return VGGP_EINVAL; }
-    VG_REQUIRE(kind >= 0 && kind <= 3 && basis >= 0 && basis <= 4, "vggp_factor_build: bad kind/basis");
+    VG_REQUIRE(kind >= 0 && kind <= 3 && basis >= 0 && basis <= 5, "vggp_factor_build: bad kind/basis");
     VG_REQUIRE(!((basis == VGGP_BASIS_VFF || basis == VGGP_BASIS_B1) && kind != VGGP_KIND_MATERN12),
                "vggp_factor_build: VFF / B1 are Matern-1/2 only");
     VG_REQUIRE(!(basis == VGGP_BASIS_B0 && kind != VGGP_KIND_MATERN12), "vggp_factor_build: B0 is Matern-1/2 only");
+    VG_REQUIRE(!(basis == VGGP_BASIS_B0K && (kind == VGGP_KIND_RBF || (flags & VGGP_FLAG_B0_F32_KDELTA))),
+               "vggp_factor_build: B0K takes Matern-1/2, -3/2, -5/2 and no VGGP_FLAG_B0_F32_KDELTA");
     VG_REQUIRE(n >= 0 && m >= 1 && ell > 0.0, "vggp_factor_build: bad sizes / lengthscale");
     VG_REQUIRE(grid || basis == VGGP_BASIS_ONE, "vggp_factor_build: null grid");
     VG_REQUIRE((x || !(A0 || dA0)), "vggp_factor_build: null x");

@@ -118,7 +118,82 @@ __device__ __forceinline__ void vg_b0_K_f32(int kd, double delta, double ell, do
     dv = 2.0 * ell * r + ell * ell * dr;
 }
 
-// one element of any basis; x = coordinate of column p (an observation for the A part, an inducing coordinate for the K part)
+// ---- B0 cells under the Matern-3/2 and Matern-5/2 kernels (VGGP_BASIS_B0K; forms, derivation and scales: tests/b0_kinds_spec.py) ----
+// c = kappa0 / ell, kappa0 = sqrt(3) or sqrt(5).  Edge function of the cross-covariance: E(g) = int_{|x-g|}^inf kappa = P(u) e^{-u} / c,
+// u = c |x - g|, P = 2 + u or (8 + 5u + u^2) / 3, and dE / d ell = Q(u) e^{-u} / kappa0, Q = 2 + 2u + u^2 or (8 + 8u + 4u^2 + u^3) / 3.
+// A cell's integral is a difference (x outside) or 2 P(0) / c minus the sum (x inside) of its two edges' terms -- only decaying
+// terms are subtracted, so a far cell keeps its relative accuracy -- and a row walk evaluates one exponential per element.
+struct VgB0kA {
+    double c, invc, invk0, in_v, in_d;      // in_v = 2 P(0) / c, in_d = 2 P(0) / kappa0: the whole-line integral and its d / d ell
+    bool n52;
+};
+__device__ __forceinline__ VgB0kA vg_b0k_A_consts(int kind, double ell) {
+    VgB0kA a;
+    a.n52 = kind == VGGP_KIND_MATERN52;
+    const double k0 = a.n52 ? 2.23606797749979 : 1.7320508075688772, P0 = a.n52 ? 8.0 / 3.0 : 2.0;
+    a.c = k0 / ell; a.invc = ell / k0; a.invk0 = 1.0 / k0;
+    a.in_v = 2.0 * P0 * a.invc; a.in_d = 2.0 * P0 * a.invk0;
+    return a;
+}
+__device__ __forceinline__ void vg_b0k_edge(const VgB0kA& a, double g, double x, double& E, double& dE) {
+    const double u = a.c * fabs(x - g), e = exp(-u);
+    const double P = a.n52 ? (8.0 + u * (5.0 + u)) * (1.0 / 3.0) : 2.0 + u;
+    const double Q = a.n52 ? (8.0 + u * (8.0 + u * (4.0 + u))) * (1.0 / 3.0) : 2.0 + u * (2.0 + u);
+    E = P * e * a.invc;
+    dE = Q * e * a.invk0;
+}
+// cell (ga, gb] from its two edges' terms
+__device__ __forceinline__ void vg_b0k_cell(const VgB0kA& a, double ga, double gb, double x, double Ea, double dEa, double Eb, double dEb,
+                                            double& v, double& dv) {
+    if (x > ga && x <= gb) { v = a.in_v - (Ea + Eb); dv = a.in_d - (dEa + dEb); }
+    else { const double sg = (x <= ga) ? 1.0 : -1.0; v = sg * (Ea - Eb); dv = sg * (dEa - dEb); }
+}
+
+// Cell-cell covariance, Toeplitz in kd = |i - j|: the second difference of G (G'' = kappa) whose linear term cancels for kd >= 1.
+// With t = c delta, x = e^{-t}, em1 = expm1(-t), q = em1^2, e2 = expm1(-2t), s2 = x^2 + 1 and E = e^{-(kd-1) t}:
+//   K0_kd = C E (a0 + kd a1 + kd^2 a2),   dK0_kd / d ell = 2 K0_kd / ell - (t / ell) C E (d0 + kd d1 + kd^2 d2 + kd^3 d3)
+// the a_i, d_i constants of the mesh (3/2: a2 = d3 = 0), C = 1 / c^2 or 1 / (3 c^2); kd = 0 is 2 G(delta) through expm1.  No factor
+// grows with t: finite for every t > 0.  One exponential per element.
+struct VgB0kK {
+    double t, toe, tol, C, a0, a1, a2, d0, d1, d2, d3, v0, dv0;      // toe = t / ell, tol = 2 / ell; v0, dv0: the diagonal
+};
+__device__ __forceinline__ VgB0kK vg_b0k_K_consts(int kind, double delta, double ell) {
+    VgB0kK k;
+    const bool n52 = kind == VGGP_KIND_MATERN52;
+    const double c = (n52 ? 2.23606797749979 : 1.7320508075688772) / ell;
+    const double t = c * delta, x = exp(-t), em1 = expm1(-t), e2 = expm1(-2.0 * t), q = em1 * em1, x2 = x * x, s2 = x2 + 1.0;
+    double b0, b1, b2, F0, dF0;
+    if (!n52) {
+        k.C = 1.0 / (c * c);
+        k.a0 = 3.0 * q + t * e2; k.a1 = t * q; k.a2 = 0.0;
+        b0 = -6.0 * x * em1 + e2 - 2.0 * t * x2; b1 = q - 2.0 * t * x * em1; b2 = 0.0;
+        F0 = 2.0 * ((3.0 + t) * em1 + 3.0 * t); dF0 = -2.0 * ((2.0 + t) * em1 + t);
+        k.d0 = k.a0 + b0; k.d1 = (k.a1 + b1) - k.a0; k.d2 = -k.a1; k.d3 = 0.0;
+    } else {
+        const double t2 = t * t;
+        k.C = 1.0 / (3.0 * c * c);
+        k.a0 = 15.0 * q + 7.0 * t * e2 + t2 * s2; k.a1 = 7.0 * t * q + 2.0 * t2 * e2; k.a2 = t2 * q;
+        b0 = -30.0 * x * em1 + 7.0 * e2 - 14.0 * t * x2 + 2.0 * t * s2 - 2.0 * t2 * x2;
+        b1 = 7.0 * q - 14.0 * t * x * em1 + 4.0 * t * e2 - 4.0 * t2 * x2;
+        b2 = 2.0 * t * q - 2.0 * t2 * x * em1;
+        F0 = 2.0 * ((15.0 + 7.0 * t + t2) * em1 + 15.0 * t + t2); dF0 = -2.0 * ((8.0 + 5.0 * t + t2) * em1 + 5.0 * t + t2);
+        k.d0 = k.a0 + b0; k.d1 = (k.a1 + b1) - k.a0; k.d2 = (k.a2 + b2) - k.a1; k.d3 = -k.a2;
+    }
+    k.t = t; k.toe = t / ell; k.tol = 2.0 / ell;
+    k.v0 = k.C * F0;
+    k.dv0 = k.tol * k.v0 - k.toe * (k.C * dF0);
+    return k;
+}
+__device__ __forceinline__ void vg_b0k_K(const VgB0kK& k, int kd, double& v, double& dv) {
+    const double kk = (double)kd, e = exp(-(double)(kd ? kd - 1 : 0) * k.t);
+    const double F = e * (k.a0 + kk * (k.a1 + kk * k.a2)), dF = e * (k.d0 + kk * (k.d1 + kk * (k.d2 + kk * k.d3)));
+    const double vk = k.C * F;
+    v = kd ? vk : k.v0;
+    dv = kd ? k.tol * vk - k.toe * (k.C * dF) : k.dv0;
+}
+
+// one element of any basis but VGGP_BASIS_B0K (whose two parts the factor kernel walks with the functions above; Matern-1/2 under B0K is
+// launched as VGGP_BASIS_B0); x = coordinate of column p (an observation for the A part, an inducing coordinate for the K part)
 __device__ __forceinline__ void vg_factor_elem(const VgFactorJob& J, bool kpart, int k, int p, double x, double gk, double gk1,
                                                double ell, double& v, double& dv) {
     const int m = J.m;

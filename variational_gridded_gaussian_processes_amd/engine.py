@@ -36,7 +36,7 @@ def _basis_m(basis: str, g: np.ndarray) -> int:
     """Number of inducing features of a dimension from its grid array."""
     if basis == "one":
         return 1
-    if basis == "b0":
+    if basis in ("b0", "b0k"):
         return len(g) - 1
     if basis == "vff":
         return 2 * (len(g) - 3) + 1
@@ -126,7 +126,7 @@ class Engine:
     def plan(self, kind1: str, basis1: str, grid1, x1, kind2: str, basis2: str, grid2, x2,
              n_total: Optional[int] = None, warm_start: bool = False, b0_f32_kdelta: bool = False,
              block_jacobi: bool = False, scattered: bool = False) -> None:
-        """grid_d: mesh (m+1 knots, basis 'b0'), inducing coordinates (m, 'points'), knot mesh (m, 'b1') or
+        """grid_d: mesh (m+1 knots, basis 'b0' or 'b0k'), inducing coordinates (m, 'points'), knot mesh (m, 'b1') or
         [a, b, omega_0 .. omega_M] (m = 2M + 1, 'vff'); x_d: the n_d unique (local) observation coordinates along d."""
         x1, x2 = _dvec(x1), _dvec(x2)
         g1 = _dvec(grid1) if basis1 != "one" else np.ones(1)

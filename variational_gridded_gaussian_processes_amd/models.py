@@ -390,8 +390,8 @@ class KroneckerStructure(torch.nn.Module):
         """The masked / scattered steps work on dense M x M matrices (M = m1 m2 <= 16384; ~10 M^2 doubles) and, for scattered points,
         on four m_d^2 x N pair-product buffers that are not chunked over N: say so here, with the numbers, instead of failing in
         hipMalloc at the first step."""
-        m1 = len(g1) - 1 if basis == "b0" else (2 * (len(g1) - 3) + 1 if basis == "vff" else len(g1))
-        m2 = len(g2) - 1 if basis == "b0" else (2 * (len(g2) - 3) + 1 if basis == "vff" else len(g2))
+        m1 = len(g1) - 1 if basis in ("b0", "b0k") else (2 * (len(g1) - 3) + 1 if basis == "vff" else len(g1))
+        m2 = len(g2) - 1 if basis in ("b0", "b0k") else (2 * (len(g2) - 3) + 1 if basis == "vff" else len(g2))
         M, N = m1 * m2, int(self._nobs)
         if M > 16384:
             raise ValueError(f"{type(self).__name__}: X is {'scattered' if self._scattered else 'a grid with holes'}, which takes the dense "
@@ -658,7 +658,7 @@ class KroneckerStructure(torch.nn.Module):
         ell = (self.kernel_1 if d == 0 else self.kernel_2).base_kernel.lengthscale.reshape(()).item()
         grid = torch.as_tensor(g1 if d == 0 else g2, dtype=torch.float64, device=self._engine.device)
         xs = torch.as_tensor(x, dtype=torch.float64, device=self._engine.device).contiguous()
-        flags = 1 if (basis == "b0" and self._f32_mesh()) else 0
+        flags = 1 if (basis == "b0" and self._f32_mesh()) else 0          # ("b0k" never carries the float32 flag)
         A, _, K, _ = self._engine.factor_build(self.kind, basis, xs, grid, ell, flags)
         return A, K
 
@@ -764,8 +764,8 @@ class _B0Gridded(KroneckerStructure):
         self.delta_2 = self.mesh_2[1] - self.mesh_2[0]
         self.b0_mesh_1, self.b0_mesh_2 = self.mesh_1, self.mesh_2
         # gridded_kronecker_structure.py:1283-1284 / kronecker_structure.py:698-699 (bspline.py:81-103)
-        self.basis_1 = B0SplineBasis(self.mesh_1, self._engine)
-        self.basis_2 = B0SplineBasis(self.mesh_2, self._engine)
+        self.basis_1 = B0SplineBasis(self.mesh_1, self._engine, kind=self.kind)
+        self.basis_2 = B0SplineBasis(self.mesh_2, self._engine, kind=self.kind)
 
     def _basis(self):
         return "b0", self.mesh_1.double().numpy(), self.mesh_2.double().numpy()
@@ -777,6 +777,30 @@ class Matern12GriddedGP(_B0Gridded):
 
 class Matern12B0SplineGriddedGP(_B0Gridded):
     """kronecker_structure.py:671-849 (identical maths)."""
+
+
+class _B0KGridded(_B0Gridded):
+    """The gridded model on the cells of VGGP_BASIS_B0K: the inducing features are the integrals of a Matern-3/2 or -5/2 process over
+    the B0 cells, so q_v() is the gridded product of a once- or twice-differentiable field.  The reference has no such model: there is
+    no float32 mesh arithmetic to reproduce, and the mesh enters as mesh.double()."""
+
+    def _basis(self):
+        return "b0k", self.mesh_1.double().numpy(), self.mesh_2.double().numpy()
+
+    def _f32_mesh(self) -> bool:
+        return False
+
+
+class Matern32GriddedGP(_B0KGridded):
+    kind = "matern32"
+
+
+class Matern52GriddedGP(_B0KGridded):
+    kind = "matern52"
+
+
+Matern32B0SplineGriddedGP = Matern32GriddedGP
+Matern52B0SplineGriddedGP = Matern52GriddedGP
 
 
 class Matern12VFFGP(KroneckerStructure):
@@ -1040,7 +1064,7 @@ class _SparseGP1D(torch.nn.Module):
         elif not self._planned or self._plan_token != self._engine.plan_token or key != self._plan_key:
             mesh = getattr(self, "mesh", None)
             self._engine.plan(self.kind, basis, g, self._x, "matern12", "one", None, np.zeros(1), warm_start=self._warm,
-                              b0_f32_kdelta=mesh is not None and mesh.dtype == torch.float32)
+                              b0_f32_kdelta=basis != "b0k" and mesh is not None and mesh.dtype == torch.float32)
             self._planned = True
             self._plan_token, self._plan_key = self._engine.plan_token, key
 
@@ -1112,10 +1136,17 @@ class univariate:
             self.mesh = torch.linspace(self.alim, self.blim, nknots)
             self.delta = self.mesh[1] - self.mesh[0]
             self.n_splines = nknots - 1
-            self.basis = B0SplineBasis(self.mesh, self._engine)       # univariate_structure.py:738
+            self.basis = B0SplineBasis(self.mesh, self._engine, kind=self.kind)       # univariate_structure.py:738
 
         def _basis(self):
-            return "b0", self.mesh.double().numpy()
+            return ("b0" if self.kind == "matern12" else "b0k"), self.mesh.double().numpy()
+
+    class Matern32B0SplineGriddedGP(Matern12B0SplineGriddedGP):
+        """the 1-D twin of Matern32GriddedGP (cells of VGGP_BASIS_B0K)"""
+        kind = "matern32"
+
+    class Matern52B0SplineGriddedGP(Matern12B0SplineGriddedGP):
+        kind = "matern52"
 
     class Matern12SVGP(_SparseGP1D):
         """univariate_structure.py:273-332."""
